@@ -7,15 +7,19 @@ L samples; each tile is an independent stream demodulated bit-exactly by one GPU
 lane (tiles of one recording are independent streams).  A "step"
 is one pass of the fused demod kernel over the whole buffer (T*L samples), input
 already in HBM.  For N>1 each rank owns its own buffer of the same shape (weak
-scaling), no collective on the data path; at N > 1 the soft symbols are then
-gathered on rank 0 over RCCL (outside the timed region; `fanin` in the JSON
-line; `--no-fanin` skips it).
+scaling), no collective on the data path; at N > 1 with --full the soft symbols
+are then gathered on rank 0 over RCCL (outside the timed region; `fanin` in the
+JSON line; `--no-fanin` skips it).
 
 One JSON line on rank 0, with `roofline` (HBM, algorithmic bytes / measured
-kernel time) and `cpu_baseline` (the reference's own code from oracle/_ref, or
-the oracle port, timed on the host cores).  The same CPU leg also verifies sampled
-tiles of the GPU output byte-for-byte against the oracle ("check"); with
---no-cpu-baseline nothing under oracle/ is touched.
+kernel time).  A plain run stops there: set-up, warm-up, the timed steps, the
+outputs of the last step if --dump-outputs is given, the line.  Everything else
+runs only with --full: `cpu_baseline` (the reference's own code from oracle/_ref,
+or the oracle port, timed on the host cores), the check of sampled tiles of the
+GPU output byte-for-byte against the oracle ("check"), the recordings, the other
+configurations, host-fed and CLI timings, and at N > 1 the `rccl` facts, the
+fan-in and the per-rank check.  With --full --no-cpu-baseline nothing under
+oracle/ is touched.
 """
 from __future__ import annotations
 
@@ -128,14 +132,24 @@ def parse() -> argparse.Namespace:
     ap.add_argument("--config", default="c1", choices=["c1", "c3", "c4"], help="c1 = the headline config")
     ap.add_argument("--fanin", action="store_true", help="(the default at N > 1 since round 5: kept so that older command lines still parse)")
     ap.add_argument("--no-fanin", action="store_true",
-                    help="N > 1: skip the gather of the soft symbols on rank 0 (RCCL over xGMI, after the timed region) and its `fanin` report")
+                    help="N > 1 with --full: skip the gather of the soft symbols on rank 0 (RCCL over xGMI, after the timed region) and its `fanin` report")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="dry run of the N > 1 path on ONE GPU: every rank on device 0, gloo for the barrier / the reductions / the "
                          "fan-in (rows staged through host memory).  Exercises the whole world > 1 control flow where only one GPU can be "
                          "reached; what it cannot show is the RCCL transport itself")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU leg")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the checks against the oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything the headline does not need: the CPU baseline, the checks against the "
+                         "oracle, the recordings, the other configurations, host-fed and CLI timings; at N > 1 the rccl facts, fan-in and "
+                         "per-rank check")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step gave its caller (soft symbols of a seeded sample of tiles, every tile's status) "
+                         "as float32 / float64 DIR/<name>.npy, at most 64 MB in all (rank 0's at N > 1)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def demod_config(tag: str):
@@ -687,6 +701,43 @@ def spot_check(cfg, d, x, tiles, L, n_check=12) -> str:
     return f"{len(picks)} sampled tiles byte-identical to oracle"
 
 
+DUMP_SOFT_BYTES = 36 << 20       # soft symbols of the sampled tiles, as float32
+DUMP_STATUS_BYTES = 20 << 20     # per-tile status (6 fields) and the tile index: 40 bytes per tile
+
+
+def dump_outputs(out_dir: str, d, soft, T: int) -> list[str]:
+    """--dump-outputs: what the last timed step handed its caller, as .npy files in `out_dir` (at most 64 MB in all).
+
+      soft.npy                [S, cap, 2] float32  the soft symbols of S <= 514 tiles (a sample seeded with 0, first and last tile
+                                                   included), 0 past each tile's symbol count
+      soft_tiles.npy          [S] float64          which tiles
+      symbols_this_call.npy, n_symbols.npy         float64, the status of every tile (or of a seeded sample of them: status_tiles.npy)
+      pll_freq.npy, omega.npy, gain.npy, locked.npy  float32
+      status_tiles.npy        float64              which tiles the status arrays belong to
+
+    The inputs are a pure function of the arguments, so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+    import torch
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    torch.cuda.synchronize()
+    st = d.status_array()
+    pick = np.unique(np.concatenate(([0, T - 1], np.random.default_rng(0).choice(T, min(T, 512), replace=False))))
+    cap = min(int(soft.shape[1]), DUMP_SOFT_BYTES // (2 * 4 * len(pick)))      # (only tiles of millions of samples lose the end of their rows)
+    rows = soft[torch.from_numpy(pick).to(soft.device), :cap].cpu().numpy().astype(np.float32)
+    counts = st["symbols_this_call"][pick].astype(np.int64)
+    rows[np.arange(cap)[None, :] >= counts[:, None]] = 0.0             # (past the count a row holds nothing the call produced)
+    n_status = DUMP_STATUS_BYTES // 40
+    sel = np.arange(T) if T <= n_status else np.sort(np.random.default_rng(1).choice(T, n_status, replace=False))
+    arrays = {"soft": rows, "soft_tiles": pick.astype(np.float64), "status_tiles": sel.astype(np.float64),
+              "symbols_this_call": st["symbols_this_call"][sel].astype(np.float64), "n_symbols": st["n_symbols"][sel].astype(np.float64),
+              "pll_freq": st["pll_freq"][sel].astype(np.float32), "omega": st["omega"][sel].astype(np.float32),
+              "gain": st["gain"][sel].astype(np.float32), "locked": st["locked"][sel].astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    return sorted(arrays)
+
+
 def spawn_ranks(args) -> int:
     """`python bench.py --gpus N` without a launcher: start N ranks (one process per GPU, RCCL rendezvous on 127.0.0.1) through
     torch.distributed.run and hand its exit code back.  Runs BEFORE anything touches the GPU in this process
@@ -956,6 +1007,10 @@ def main() -> None:
     elapsed = time.perf_counter() - t0
     kernel_ms = sum(a.elapsed_time(b) for a, b in ev) / max(1, len(ev))
     elapsed_here, kernel_ms_here = elapsed, kernel_ms
+    if args.dump_outputs and rank == 0:
+        # before anything else touches the context or `soft`: what the last timed step handed its caller
+        names = dump_outputs(args.dump_outputs, d, soft, T)
+        sys.stderr.write(f"bench.py: outputs of the last timed step in {args.dump_outputs}: {', '.join(n + '.npy' for n in names)}\n")
 
     # ---- the timed region is over: from here on nothing may lose it -------------------------------------------------------------
     # Rank 0 holds the record of THIS rank's clock already; the max over ranks replaces it if the reduction below succeeds.
@@ -1040,6 +1095,7 @@ def main() -> None:
         if stage("reduce_times", reduce_times) is None and rank == 0:
             full["value_note"] = "rank 0's own clock: the max-over-ranks reduction failed (see errors)"
 
+    if dist and args.full:
         def rccl_facts():
             # did the collective layer see every rank, and which device is each on?
             ones = torch.ones(1, dtype=torch.int32, device=coll_dev)
@@ -1058,7 +1114,7 @@ def main() -> None:
                             "distinct_devices": len(set(devs)), "rccl_version": ver}
         stage("rccl", rccl_facts)
 
-    if dist and not args.no_fanin:
+    if dist and args.full and not args.no_fanin:
         def fanin():
             # fan-in of the soft symbols to rank 0 over RCCL (outside the timed region): rows compacted on the device to the
             # nominal symbol pitch first (0.63 B per input sample instead of the hard-bound 2 B), then exact-size send/recv
@@ -1101,7 +1157,7 @@ def main() -> None:
         torch.cuda.empty_cache()
 
     # every rank checks sampled tiles of ITS buffer against the oracle (the checker, after the timed region); rank 0 reports
-    if dist and not args.no_check:
+    if dist and args.full and not args.no_check:
         def check_ranks():
             try:
                 verdict = spot_check(cfg, d, x, T, L, n_check=2)
@@ -1124,7 +1180,7 @@ def main() -> None:
                 pass
         return
 
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         # The CPU leg: the only place in this file that touches oracle/ — it times the reference's own
         # code on the host cores and (unless --no-check) uses the oracle as CHECKER on sampled tiles.
         def put(key, fn):

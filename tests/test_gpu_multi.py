@@ -35,7 +35,7 @@ def _line_ok(line, n1):
 @pytest.mark.parametrize("config", ["c1", "c3"])
 def test_bench_two_ranks_oversubscribed_on_one_gpu(gpu_device, config):
     T, L = 4096, 4160
-    r, lines = _bench("--gpus", "2", "--oversubscribe", "--config", config, "--tiles", str(T), "--tile-samples", str(L), "--steps", "2", "--warmup", "1")       # (no --fanin: the gather on rank 0 is the default at N > 1 since round 5)
+    r, lines = _bench("--gpus", "2", "--oversubscribe", "--config", config, "--tiles", str(T), "--tile-samples", str(L), "--steps", "2", "--warmup", "1", "--full")       # (no --fanin: with --full the gather on rank 0 is the default at N > 1)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1, r.stdout                                  # rank 0 prints ONE line, the other rank nothing
     assert r.stdout.strip().splitlines()[-1] == lines[0]              # ... and it is the LAST thing on stdout
@@ -53,7 +53,7 @@ def test_bench_two_ranks_oversubscribed_on_one_gpu(gpu_device, config):
 
 
 def test_bench_two_ranks_no_fanin_flag(gpu_device):
-    r, lines = _bench("--gpus", "2", "--oversubscribe", "--tiles", "4096", "--tile-samples", "4160", "--steps", "1", "--warmup", "0", "--no-fanin", "--no-check")
+    r, lines = _bench("--gpus", "2", "--oversubscribe", "--tiles", "4096", "--tile-samples", "4160", "--steps", "1", "--warmup", "0", "--full", "--no-fanin", "--no-check")
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(lines[0])
     assert "fanin" not in d and d["n_gpus"] == 2
@@ -73,7 +73,7 @@ def test_bench_line_survives_a_fault_after_the_timed_region(gpu_device, fault, d
     (the others then wait in a collective nobody completes), a rank that hangs - the line still appears, once, rc 0, with the
     timed fields and the error text."""
     T, L = 4096, 4160
-    r, lines = _bench("--gpus", "2", "--oversubscribe", "--tiles", str(T), "--tile-samples", str(L), "--steps", "2", "--warmup", "1",
+    r, lines = _bench("--gpus", "2", "--oversubscribe", "--tiles", str(T), "--tile-samples", str(L), "--steps", "2", "--warmup", "1", "--full",
                       env={"MDEMOD_BENCH_FAULT": fault, "MDEMOD_BENCH_POST_DEADLINE_S": deadline}, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1, r.stdout
@@ -87,15 +87,56 @@ def test_bench_line_survives_a_fault_after_the_timed_region(gpu_device, fault, d
 
 
 def test_bench_default_line_is_compact(gpu_device):
-    """The N = 1 line at a small shape with the CPU leg on: required keys first, roofline and cpu_baseline complete, under the
-    hard bound, the long record in bench_extras.json."""
-    r, lines = _bench("--tiles", "8192", "--tile-samples", "4160", "--steps", "2", "--warmup", "1", "--no-check")
+    """The N = 1 line of a --full run at a small shape with the CPU leg on: required keys first, roofline and cpu_baseline complete,
+    under the hard bound, the long record in bench_extras.json."""
+    r, lines = _bench("--tiles", "8192", "--tile-samples", "4160", "--steps", "2", "--warmup", "1", "--full", "--no-check")
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1 and r.stdout.strip().splitlines()[-1] == lines[0]
     d = _line_ok(lines[0], n1=True)
     full = json.loads((ROOT / "bench_extras.json").read_text())
     assert full["value"] == d["value"] and "other_configs" in full and "host_fed" in full
     assert "bench.py full record: {" in r.stderr
+
+
+def test_bench_plain_run_is_lean_and_dumps_what_it_computed(gpu_device, tmp_path):
+    """A plain N = 1 run (no --full): the headline and its roofline, none of the CPU leg, the checks or the extras; `--steps` timed
+    steps and `ms_per_step` their mean.  --dump-outputs writes what the last timed step computed, as float32 / float64 .npy files: the
+    same files from two runs with the same arguments, the oracle's bytes for the sampled tiles (their 4th block: 1 warm-up + 3 steps)."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT / "tests"))
+    import oracle_py as O
+    from meteor_demod_amd import DemodConfig, synth
+    T, L = 4096, 4160
+    dumps = []
+    for k in range(2):
+        r, lines = _bench("--tiles", str(T), "--tile-samples", str(L), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / f"run{k}"))
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len(lines) == 1 and r.stdout.strip().splitlines()[-1] == lines[0]
+        d = _line_ok(lines[0], n1=False)
+        assert "errors" not in d and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+        assert d["value"] > 0 and abs(d["value"] - T * L / (d["ms_per_step"] * 1e-3) / 1e6) < 0.01 * d["value"]
+        assert not {"cpu_baseline", "check", "useful", "other_configs", "host_fed", "cli_2p26_wav_seconds", "rccl", "fanin"} & set(d), sorted(d)
+        files = sorted((tmp_path / f"run{k}").glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        dumps.append({f.stem: np.load(f) for f in files})
+    a, b = dumps
+    assert set(a) == {"soft", "soft_tiles", "status_tiles", "symbols_this_call", "n_symbols", "pll_freq", "omega", "gain", "locked"}
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and a[name].tobytes() == b[name].tobytes(), name
+    tiles = a["soft_tiles"].astype(np.int64)
+    assert tiles[0] == 0 and tiles[-1] == T - 1 and len(tiles) > 64 and np.array_equal(a["status_tiles"], np.arange(T))
+    cfg = DemodConfig(samplerate=230000)
+    st = synth.make_stream(1000, cfg.samplerate, cfg.symrate, f0_hz=1200.0, clock_ppm=-3.5)       # bench.py's recording at N = 1
+    for row, t in ((0, 0), (len(tiles) // 2, int(tiles[len(tiles) // 2])), (len(tiles) - 1, T - 1)):
+        x = synth.generate_host(st, L, n0=t * L)
+        o = O.OracleStream(cfg)
+        for _ in range(3):
+            o.run(x)
+        want = o.run(x)[0]
+        m = int(a["symbols_this_call"][t])
+        assert m == want.shape[0] and np.array_equal(a["soft"][row, :m], want.astype(np.float32)), t
+        assert not a["soft"][row, m:].any()
+        assert a["n_symbols"][t] == o.state.n_symbols and a["pll_freq"][t] == np.float32(o.state.pll_freq)
 
 
 def test_fanin_peer_gathers_the_rows_of_several_contexts(gpu_device):

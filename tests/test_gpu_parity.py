@@ -1033,12 +1033,8 @@ def test_random_option_combinations_match_oracle(idx, gpu_device):
             assert np.float32(st[i].pll_freq) == np.float32(ost.state.pll_freq) and st[i].locked == ost.state.locked
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref (the reference built from /root/reference) did not travel with this checkout")
-@pytest.mark.parametrize("seed", [21, 22])
-def test_hip_equals_the_live_reference(seed, gpu_device, kernel_variant):
-    """Not through the restatement: the HIP path against the REFERENCE ITSELF (oracle/_ref/ref_harness = the reference's own objects,
-    built in the survey container and carried along) on random settings - every kernel variant, byte for byte."""
-    torch = _torch()
+def live_reference_cases(seed: int):
+    """The 8 random settings of `seed` (cfg, iq) on which the HIP path meets the reference itself."""
     rng = np.random.default_rng(seed)
     done = 0
     while done < 8:
@@ -1050,11 +1046,26 @@ def test_hip_equals_the_live_reference(seed, gpu_device, kernel_variant):
             continue
         st = synth.make_stream(int(rng.integers(1, 1 << 30)), cfg.samplerate, cfg.symrate, oqpsk=oqpsk, f0_hz=float(rng.uniform(-900, 900)), esn0_db=14.0,
                                fmt=cfg.bps, **({"rms": 40.0} if cfg.bps == 8 else {"rms": 0.3} if cfg.bps == 32 else {}))
-        iq = synth.generate_host(st, int(2500 * cfg.samplerate / cfg.symrate))
-        want, _ = O.ref_demod(cfg, iq)
+        yield cfg, synth.generate_host(st, int(2500 * cfg.samplerate / cfg.symrate))
+        done += 1
+
+
+@pytest.mark.parametrize("seed", [21, 22])
+def test_hip_equals_the_live_reference(seed, gpu_device, kernel_variant):
+    """Not through the restatement: the HIP path against the REFERENCE ITSELF (oracle/_ref/ref_harness = the reference's own objects,
+    built in the survey container and carried along, where it is there; everywhere against the digests of its outputs for the same
+    inputs, tests/golden/live_reference.json) on random settings - every kernel variant, byte for byte."""
+    import json
+    torch = _torch()
+    stored = json.loads((O.ROOT / "tests" / "golden" / "live_reference.json").read_text())["hip"][str(seed)]
+    for k, (cfg, iq) in enumerate(live_reference_cases(seed)):
+        want = O.ref_demod(cfg, iq)[0] if O.have_ref() else None
         with Demodulator(cfg, 3) as d:
             soft = d.process(torch.from_numpy(np.stack([iq, iq, iq])).cuda())
             torch.cuda.synchronize()
             m = d.status(2, 1)[0].symbols_this_call
-            assert m == want.shape[0] and np.array_equal(soft[2, :m].cpu().numpy(), want), (cfg, d.kernel_name)
-        done += 1
+            got = soft[2, :m].cpu().numpy()
+            if want is not None:
+                assert m == want.shape[0] and np.array_equal(got, want), (cfg, d.kernel_name)
+            assert m == stored[k]["symbols"] and sha(got) == stored[k]["soft"], (cfg, d.kernel_name)
+    assert k + 1 == len(stored)

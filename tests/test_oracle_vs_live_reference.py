@@ -4,17 +4,27 @@ this draws a few hundred more - sample rates from 0.4 to 150 samples per symbol,
 ranges, the three input formats, QPSK and OQPSK, the region where every interpolated step fires - and asks for the same soft bytes and
 the same per-symbol floats (symbol, PLL frequency, clock word, AGC gain, lock flag), bit for bit.
 
-Runs wherever oracle/_ref was built (this container: build() makes it; the prebuilt binary travels to the GPU box); skipped elsewhere.
-Test infrastructure only: nothing here touches the product path."""
+Where oracle/_ref was built, the reference runs live; everywhere the outputs are also held against digests of the reference's own
+outputs for the same seeded inputs (tests/golden/live_reference.json, recorded by tests/golden/make_live_digests.py), so a checkout
+without the reference's sources checks the same bytes.  Test infrastructure only: nothing here touches the product path."""
 from __future__ import annotations
+
+import json
+from pathlib import Path
 
 import numpy as np
 import pytest
 
 import oracle_py as O
+from golden_cases import sha
 from meteor_demod_amd import DemodConfig, synth
 
-pytestmark = pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref (the reference built from /root/reference) is not here")
+DIGESTS = Path(__file__).resolve().parent / "golden" / "live_reference.json"
+
+
+def stored(key: str):
+    """Digests of the reference's own outputs (tests/golden/make_live_digests.py)."""
+    return json.loads(DIGESTS.read_text())[key]
 
 
 def _settings(seed: int, count: int):
@@ -41,10 +51,8 @@ def _settings(seed: int, count: int):
     return out
 
 
-@pytest.mark.timeout(600)
-@pytest.mark.parametrize("seed", [11, 12, 13, 14])
-def test_restatement_equals_the_live_reference(seed):
-    checked = 0
+def restatement_cases(seed: int):
+    """(cfg, stream seed, iq) of every setting of `seed` the reference is defined on."""
     for cfg, s, f0, esn0 in _settings(seed, 150):
         table = O.OracleStream(cfg).rrc_table()
         if not np.isfinite(table).all():                      # 0/0 on a tap (filter.c:86-93): the reference then indexes its LUT out of bounds
@@ -52,26 +60,31 @@ def test_restatement_equals_the_live_reference(seed):
         st = synth.make_stream(s, cfg.samplerate, cfg.symrate, oqpsk=cfg.oqpsk, f0_hz=f0, esn0_db=esn0, fmt=cfg.bps,
                                **({"rms": 40.0} if cfg.bps == 8 else {"rms": 0.3} if cfg.bps == 32 else {}))
         n = int(min(60000, max(4000, 3000 * cfg.samplerate / cfg.symrate)))
-        iq = synth.generate_host(st, n)
-        want_soft, want_trace = O.ref_demod(cfg, iq, want_trace=True)
-        got_soft, got_trace, _ev = O.oracle_demod(cfg, iq, want_trace=True)
-        assert got_soft.shape == want_soft.shape and np.array_equal(got_soft, want_soft), (cfg, s)
-        assert got_trace.tobytes() == want_trace.tobytes(), (cfg, s)        # every float of every symbol, bit for bit
-        checked += 1
-    assert checked >= 130
+        yield cfg, s, synth.generate_host(st, n)
 
 
 @pytest.mark.timeout(600)
-@pytest.mark.skipif(not O.REF_BINARY.exists(), reason="the reference's own CLI binary is not here")
-def test_file_model_equals_the_live_reference_binary(tmp_path):
-    """The file level (SURVEY H7: whole 32 KiB reads, 1024-byte chunks behind the lock gate, the double-length final flush): the
-    oracle's file model against the reference's own CLI binary on random files - WAV and raw, the three formats, QPSK / OQPSK, -O / -f /
-    -b, lengths that end anywhere inside a read.  (Lengths whose last chunk is more than half full make the reference's final flush
-    read past its ring, main.c:321: those are trimmed away here as in tests/golden/make_golden.py.)"""
-    import subprocess
+@pytest.mark.parametrize("seed", [11, 12, 13, 14])
+def test_restatement_equals_the_live_reference(seed):
+    want = stored("restatement")[str(seed)]
+    checked = 0
+    for cfg, s, iq in restatement_cases(seed):
+        got_soft, got_trace, _ev = O.oracle_demod(cfg, iq, want_trace=True)
+        if O.have_ref():
+            want_soft, want_trace = O.ref_demod(cfg, iq, want_trace=True)
+            assert got_soft.shape == want_soft.shape and np.array_equal(got_soft, want_soft), (cfg, s)
+            assert got_trace.tobytes() == want_trace.tobytes(), (cfg, s)        # every float of every symbol, bit for bit
+        w = want[checked]
+        assert got_soft.shape[0] == w["symbols"] and sha(got_soft) == w["soft"], (cfg, s)
+        assert sha(got_trace) == w["trace"], (cfg, s)
+        checked += 1
+    assert checked >= 130 and checked == len(want)
+
+
+def file_cases():
+    """(case, cfg, container, cli args, samples, file bytes) of the random files (only lengths the reference's flush defines)."""
     from golden_cases import wav_header
     rng = np.random.default_rng(2025)
-    checked = locked_cases = 0
     for case in range(44):
         oqpsk = bool(rng.random() < 0.35)
         bps = int(rng.choice([8, 16, 16, 32]))
@@ -99,13 +112,30 @@ def test_file_model_equals_the_live_reference_binary(tmp_path):
         if container == "raw":
             args += ["-s", str(fs), "--bps", str(bps)]
         data = (wav_header(fs, bps, len(body)) if container == "wav" else b"") + body
-        inp, out = tmp_path / f"in{case}.{container}", tmp_path / f"out{case}.s"
-        inp.write_bytes(data)
-        subprocess.run([str(O.REF_BINARY), "-q", "-B", "-o", str(out), *args, str(inp)], check=True, capture_output=True, timeout=120)
-        want = out.read_bytes()
-        got = O.OracleStream(cfg).file_model(body, bps)
-        assert got == want, (case, cfg, container, len(body), len(got), len(want))
+        yield case, cfg, container, args, body, data
+
+
+@pytest.mark.timeout(600)
+def test_file_model_equals_the_live_reference_binary(tmp_path):
+    """The file level (SURVEY H7: whole 32 KiB reads, 1024-byte chunks behind the lock gate, the double-length final flush): the
+    oracle's file model against the reference's own CLI binary on random files - WAV and raw, the three formats, QPSK / OQPSK, -O / -f /
+    -b, lengths that end anywhere inside a read.  (Lengths whose last chunk is more than half full make the reference's final flush
+    read past its ring, main.c:321: those are trimmed away here as in tests/golden/make_golden.py.)  The binary runs where it was
+    built; its outputs' digests are checked everywhere."""
+    import hashlib
+    import subprocess
+    want = stored("file_model")
+    checked = locked_cases = 0
+    for case, cfg, container, args, body, data in file_cases():
+        got = O.OracleStream(cfg).file_model(body, cfg.bps)
+        if O.REF_BINARY.exists():
+            inp, out = tmp_path / f"in{case}.{container}", tmp_path / f"out{case}.s"
+            inp.write_bytes(data)
+            subprocess.run([str(O.REF_BINARY), "-q", "-B", "-o", str(out), *args, str(inp)], check=True, capture_output=True, timeout=120)
+            assert got == out.read_bytes(), (case, cfg, container, len(body), len(got), len(out.read_bytes()))
+            inp.unlink(); out.unlink()
+        w = want[str(case)]
+        assert len(got) == w["bytes"] and hashlib.sha256(got).hexdigest() == w["sha256"], (case, cfg, container, len(body), len(got), w["bytes"])
         checked += 1
-        locked_cases += len(want) > 2048
-        inp.unlink(); out.unlink()
-    assert checked >= 30 and locked_cases >= 20
+        locked_cases += len(got) > 2048
+    assert checked >= 30 and locked_cases >= 20 and checked == len(want)
