@@ -23,6 +23,10 @@
  * with -B and redrawn in place otherwise.  On a terminal, without -B / -q / --tiled, the full-screen display of the reference
  * (tui.c; main.c:197,224-245) is drawn instead: host/tui.c, built in when ncurses is there (as the reference's ENABLE_TUI).
  * Unlike the reference it is not started when stdin or stdout is not a terminal, unless --tui asks for it.
+ * --offset <Hz> / --decimate <N> put the front end of include/meteor_demod_amd_frontend.h in front of the demodulator: the signal
+ * is moved from <Hz> off the recording's centre to 0 Hz, filtered and decimated on the GPU, and demodulated at fs / N.  -s / --bps
+ * (or the WAV header) describe the recording as always.  Its entries are weak references: this program still links against a
+ * library without them (and says so when asked for the front end).
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -39,6 +43,7 @@
 #include <unistd.h>
 
 #include "meteor_demod_amd.h"
+#include "meteor_demod_amd_frontend.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
 #endif
@@ -70,8 +75,38 @@ static const struct option longopts[] = {
 	{ "device", 1, NULL, 0x01 },    { "tiled", 0, NULL, 0x02 },   { "tile-samples", 1, NULL, 0x03 },
 	{ "pilot-margin", 1, NULL, 0x04 }, { "carrier-seed", 1, NULL, 0x05 }, { "devices", 1, NULL, 0x06 }, { "plan", 0, NULL, 0x07 },
 	{ "tui-selftest", 0, NULL, 0x08 }, { "tui", 0, NULL, 0x09 }, { "jobs", 1, NULL, 0x0a },
+	{ "offset", 1, NULL, 0x0b },    { "decimate", 1, NULL, 0x0c },
 	{ NULL, 0, NULL, 0 }
 };
+
+/* the front end's entries: weak, so that the program links (and runs without --offset / --decimate) against a library that has none */
+#pragma weak mdemod_fe_design
+#pragma weak mdemod_fe_create
+#pragma weak mdemod_fe_destroy
+#pragma weak mdemod_fe_demodulator
+#pragma weak mdemod_fe_process_host
+#pragma weak mdemod_fe_demodulate_recording_host
+
+static int
+have_frontend(void)
+{
+	return mdemod_fe_design && mdemod_fe_create && mdemod_fe_destroy && mdemod_fe_demodulator && mdemod_fe_process_host &&
+	       mdemod_fe_demodulate_recording_host;
+}
+
+/* --offset: a signed number of Hz with an optional k / M suffix (fractions kept); 1 on a malformed one */
+static int
+parse_hz(const char *s, double *out)
+{
+	char *end;
+	double v = strtod(s, &end);
+	if (end == s) return 1;
+	if (*end == 'k' || *end == 'K') { v *= 1e3; end++; }
+	else if (*end == 'M') { v *= 1e6; end++; }
+	if (*end) return 1;
+	*out = v;
+	return 0;
+}
 
 /* utils.c:60-86: number with optional k/M suffix, truncated to int, returned as float */
 static float
@@ -113,6 +148,11 @@ usage(const char *prog)
 	        "                           --carrier-seed spectrum|pilot (default spectrum: tiles follow Doppler);\n"
 	        "                           --jobs <n>: files of one GPU in flight at once (default 4: their serial heads\n"
 	        "                           and file reads overlap)\n"
+	        "       --offset <hz>       The signal sits <hz> from the recording's centre (k/M suffixes, may be negative):\n"
+	        "                           a front end on the GPU moves it to 0 Hz before the demodulator\n"
+	        "       --decimate <n>      The front end low-pass filters and keeps every n-th sample (1..128; the sample\n"
+	        "                           rate must be a multiple of n, and rate / n at least 2.4 x the symbol rate); the\n"
+	        "                           demodulator runs at rate / n.  Either option turns the front end on\n"
 	        "   -h, --help   -v, --version\n", prog);
 }
 
@@ -250,6 +290,8 @@ struct worker {
 	int         tiled, quiet, batch, update_interval, tile_samples, pilot_margin, carrier_seed;
 	int         tui;                     /* worker 0 only: the full-screen display is up */
 	int         jobs;                    /* --tiled: files of this worker in flight at once */
+	int         use_fe;                  /* --offset / --decimate: the front end ahead of the demodulator */
+	mdemod_fe_params fe;
 	int         rc;                      /* exit code of this worker: 0 ok, 1 host error, 2 library error */
 };
 
@@ -321,10 +363,11 @@ tiled_one_file(struct worker *w, int f)
 	if (carrier_seed >= 0) ro.carrier_seed = (uint32_t)carrier_seed;
 	mdemod_recording_report rr;
 	const double t_read = now_ms();
-	int rc2 = mdemod_demodulate_recording_host(&p, &ro, data, n_samples, soft_all, cap_sym, &rr);
+	int rc2 = w->use_fe ? mdemod_fe_demodulate_recording_host(&p, &w->fe, &ro, data, n_samples, soft_all, cap_sym, &rr)
+	                    : mdemod_demodulate_recording_host(&p, &ro, data, n_samples, soft_all, cap_sym, &rr);
 	const double t_lib = now_ms();
 	if (rc2 != MDEMOD_OK) {
-		fprintf(stderr, "mdemod_demodulate_recording_host: %s\n", why_of(rc2));
+		fprintf(stderr, "%s: %s\n", w->use_fe ? "mdemod_fe_demodulate_recording_host" : "mdemod_demodulate_recording_host", why_of(rc2));
 		free(data); free(soft_all);
 		return 2;
 	}
@@ -419,8 +462,13 @@ run_exact(struct worker *w)
 	const float symrate = (float)w->p.symrate;
 	mdemod_params p = w->p;
 	mdemod_ctx *ctx = NULL;
-	int rc = mdemod_create(&p, &ctx);
-	if (rc != MDEMOD_OK) return exact_failed(w, 2, "mdemod_create", why_of(rc));
+	mdemod_fe *fe = NULL;
+	const int D = w->use_fe ? w->fe.decimation : 1;
+	int rc = w->use_fe ? mdemod_fe_create(&p, &w->fe, &fe) : mdemod_create(&p, &ctx);
+	if (rc != MDEMOD_OK) return exact_failed(w, 2, w->use_fe ? "mdemod_fe_create" : "mdemod_create", why_of(rc));
+	if (fe) ctx = mdemod_fe_demodulator(fe);
+	/* (the context goes with its front end when there is one) */
+#define DESTROY_CTX() do { if (fe) mdemod_fe_destroy(fe); else mdemod_destroy(ctx); } while (0)
 	if (!quiet) say("Demodulator initialized\n");                                    /* main.c:219 */
 	if (!quiet && !w->tui && n_files < 64 && io[0].file_len > (64ul << 20))
 		fprintf(stderr, "note: %d file%s demodulated exactly = %d serial stream%s, one GPU wavefront each (about 3.6 MS/s: slower than the "
@@ -432,7 +480,7 @@ run_exact(struct worker *w)
 	for (int i = 0; i < n_files; i++) if (io[i].in == stdin) block_buffers = PIPE_BUFFERS;     /* live input: short blocks */
 	const size_t block_bytes = block_buffers * FILE_BUFFER_SIZE;
 	const uint32_t block_samples = (uint32_t)(block_bytes / (2 * (size_t)bps / 8));
-	const uint32_t cap = (uint32_t)mdemod_max_symbols(ctx, block_samples);
+	const uint32_t cap = (uint32_t)mdemod_max_symbols(ctx, (block_samples + (uint32_t)D - 1) / (uint32_t)D);
 	unsigned char *in_buf = malloc(block_bytes * (size_t)n_files);
 	int8_t *soft = malloc((size_t)cap * 2 * (size_t)n_files);
 	const void **iq = malloc(sizeof(*iq) * (size_t)n_files);
@@ -441,12 +489,12 @@ run_exact(struct worker *w)
 	uint32_t *n_out = malloc(sizeof(uint32_t) * (size_t)n_files);
 	mdemod_status *st = malloc(sizeof(*st) * (size_t)n_files);
 #define FREE_BLOCKS() do { free(in_buf); free(soft); free(iq); free(outp); free(n_in); free(caps); free(n_out); free(st); } while (0)
-	if (!in_buf || !soft || !iq || !outp || !n_in || !caps || !n_out || !st) { mdemod_destroy(ctx); FREE_BLOCKS(); return exact_failed(w, 1, "meteor_demod_amd", "out of memory"); }
+	if (!in_buf || !soft || !iq || !outp || !n_in || !caps || !n_out || !st) { DESTROY_CTX(); FREE_BLOCKS(); return exact_failed(w, 1, "meteor_demod_amd", "out of memory"); }
 
 	/* the read buffer is the same for every block: pinned once, the batch then goes to the GPU from where fread put it
 	   (a batch of files; one file is a few MiB per call either way.  A refusal - no memory to pin - only means the library stages the
 	   blocks itself.  The context is destroyed, which unpins, BEFORE the buffer is freed on every way out.) */
-	if (n_files >= 2 && block_buffers == BLOCK_BUFFERS) (void)mdemod_pin_host_buffer(ctx, in_buf, block_bytes * (size_t)n_files);
+	if (!fe && n_files >= 2 && block_buffers == BLOCK_BUFFERS) (void)mdemod_pin_host_buffer(ctx, in_buf, block_bytes * (size_t)n_files);
 
 	double last_status = -1e18;
 #ifdef MDEMOD_TUI
@@ -468,10 +516,11 @@ run_exact(struct worker *w)
 			if (got) active = 1;
 		}
 		if (!active) break;
-		rc = mdemod_process_host(ctx, iq, n_in, outp, caps, n_out);          /* demod(&sample) x n: main.c:304 */
-		if (rc != MDEMOD_OK) { const char *why = why_of(rc); mdemod_destroy(ctx); FREE_BLOCKS(); return exact_failed(w, 2, "mdemod_process_host", why); }
+		rc = fe ? mdemod_fe_process_host(fe, iq, n_in, outp, caps, n_out)
+		        : mdemod_process_host(ctx, iq, n_in, outp, caps, n_out);          /* demod(&sample) x n: main.c:304 */
+		if (rc != MDEMOD_OK) { const char *why = why_of(rc); DESTROY_CTX(); FREE_BLOCKS(); return exact_failed(w, 2, fe ? "mdemod_fe_process_host" : "mdemod_process_host", why); }
 		rc = mdemod_get_status(ctx, 0, (uint32_t)n_files, st, NULL);
-		if (rc != MDEMOD_OK) { const char *why = why_of(rc); mdemod_destroy(ctx); FREE_BLOCKS(); return exact_failed(w, 2, "mdemod_get_status", why); }
+		if (rc != MDEMOD_OK) { const char *why = why_of(rc); DESTROY_CTX(); FREE_BLOCKS(); return exact_failed(w, 2, "mdemod_get_status", why); }
 		for (int i = 0; i < n_files; i++)
 			write_gated(&io[i], outp[i], n_out[i], st[i].first_lock_symbol);
 #ifdef MDEMOD_TUI
@@ -483,8 +532,9 @@ run_exact(struct worker *w)
 		if (!quiet && now_ms() - last_status >= update_interval) {
 			/* main.c:249-261: status line from the snapshot of stream 0, at most once per refresh period */
 			last_status = now_ms();
-			const double freq_hz = st[0].pll_freq * symrate / (2 * M_PI) * (oqpsk ? 2 : 1);
-			const double rate_hz = st[0].omega * ((double)samplerate * interp) / (2 * M_PI);
+			/* with the front end: the carrier from the recording's centre (offset + the PLL's estimate), the clock at fs / D */
+			const double freq_hz = st[0].pll_freq * symrate / (2 * M_PI) * (oqpsk ? 2 : 1) + (fe ? w->fe.offset_hz : 0.0);
+			const double rate_hz = st[0].omega * ((double)(samplerate / D) * interp) / (2 * M_PI);
 			const long pos = io[0].in != stdin ? ftell(io[0].in) : 0;
 #ifdef MDEMOD_TUI
 			if (w->tui) {
@@ -513,9 +563,10 @@ run_exact(struct worker *w)
 		if (io[i].in != stdin) fclose(io[i].in);
 		io[i].in = NULL;
 	}
-	mdemod_destroy(ctx);                                                          /* demod_deinit: main.c:273 */
+	DESTROY_CTX();                                                                /* demod_deinit: main.c:273 */
 	FREE_BLOCKS();
 #undef FREE_BLOCKS
+#undef DESTROY_CTX
 #ifdef MDEMOD_TUI
 	if (w->tui) {                                                                 /* main.c:241-244 */
 		say("Demodulation complete\n");
@@ -564,6 +615,8 @@ main(int argc, char **argv)
 	int tile_samples = 0, pilot_margin = -1, carrier_seed = -1, update_interval = -1;
 	const char *output_fname = NULL;
 	int devs[MAX_DEVICES], n_dev = 0, plan = 0, jobs = 4;
+	int use_fe = 0, decimation = 1;
+	double offset_hz = 0.0;
 #ifdef MDEMOD_TUI
 	int force_tui = 0;
 #endif
@@ -584,6 +637,18 @@ main(int argc, char **argv)
 		case 0x09: break;                             /* --tui in a build without the display: accepted, nothing to draw */
 #endif
 		case 0x0a: jobs = atoi(optarg); if (jobs < 1) { fprintf(stderr, "--jobs: a positive number\n"); return 1; } break;
+		case 0x0b:
+			if (parse_hz(optarg, &offset_hz)) { fprintf(stderr, "--offset: a number of Hz (k/M suffixes), e.g. 300k or -1.2M\n"); return 1; }
+			use_fe = 1;
+			break;
+		case 0x0c: {
+			char *end;
+			const long v = strtol(optarg, &end, 10);
+			if (end == optarg || *end || v < 1 || v > 1 << 20) { fprintf(stderr, "--decimate: a positive integer\n"); return 1; }
+			decimation = (int)v;
+			use_fe = 1;
+			break;
+		}
 		case 0x08:
 #ifdef MDEMOD_TUI
 			return tui_selftest(force_tui);
@@ -624,6 +689,10 @@ main(int argc, char **argv)
 	const int n_files = argc - optind;
 	if (n_files > 1 && (output_fname || stdout_mode)) {
 		fprintf(stderr, "-o/--stdout need a single input file\n");
+		return 1;
+	}
+	if (use_fe && !have_frontend()) {
+		fprintf(stderr, "--offset / --decimate: this library has no front end (built without include/meteor_demod_amd_frontend.h's entries)\n");
 		return 1;
 	}
 	if (plan) {
@@ -670,6 +739,17 @@ main(int argc, char **argv)
 	 * output file; same here, without touching the GPU */
 	const int bps_ok = (bps == 8 || bps == 16 || bps == 32);
 	if (!bps_ok) fprintf(stderr, "%d bits per sample: nothing to demodulate (8, 16 or 32 expected)\n", bps);
+	mdemod_fe_params fep;
+	memset(&fep, 0, sizeof(fep));
+	fep.offset_hz = offset_hz; fep.decimation = decimation; fep.taps_per_phase = 0;
+	if (use_fe && bps_ok) {
+		/* the front end's settings are checked on the host, before any output file or the GPU: a refusal leaves nothing behind */
+		mdemod_params in;
+		memset(&in, 0, sizeof(in));
+		in.samplerate = samplerate; in.symrate = (int)symrate; in.bps = bps; in.n_streams = 1;
+		const int rc = mdemod_fe_design(&in, &fep, NULL, 0, NULL, NULL);
+		if (rc != MDEMOD_OK) { fprintf(stderr, "--offset / --decimate: %s\n", why_of(rc)); LEAVE(1); }
+	}
 
 	for (int i = 0; i < n_files; i++) {
 		if (stdout_mode) { io[i].out = stdout; continue; }
@@ -734,6 +814,7 @@ main(int argc, char **argv)
 		w->tile_samples = tile_samples; w->pilot_margin = pilot_margin; w->carrier_seed = carrier_seed;
 		w->tui = use_tui && d == 0;
 		w->jobs = jobs;
+		w->use_fe = use_fe; w->fe = fep;
 		for (int i = d; i < n_files; i += n_dev) w->n_files++;
 		w->io = calloc((size_t)w->n_files, sizeof(*w->io));
 		if (!w->io) LEAVE(1);

@@ -6,5 +6,7 @@ built shared library (lib/) and a thin host-side mirror of the reference's
 interface (demod.py).  Nothing here computes on the CPU.
 """
 from .demod import DemodConfig, Demodulator, derive_tables, scale_freq_max  # noqa: F401
+from .frontend import FrontEnd, FrontEndConfig, demodulate_recording_frontend, design_taps  # noqa: F401
 
-__all__ = ["DemodConfig", "Demodulator", "derive_tables", "scale_freq_max"]
+__all__ = ["DemodConfig", "Demodulator", "derive_tables", "scale_freq_max",
+           "FrontEnd", "FrontEndConfig", "demodulate_recording_frontend", "design_taps"]

@@ -152,7 +152,7 @@ def check_rot_partition(files: dict | None = None) -> list[str]:
 def build(force: bool = False, verbose: bool = False) -> dict[str, Path]:
     LIB.mkdir(exist_ok=True)
     hipcc = _hipcc()
-    headers = sorted(CSRC.glob("*.h")) + [ROOT / "include" / "meteor_demod_amd.h"]
+    headers = sorted(CSRC.glob("*.h")) + sorted((ROOT / "include").glob("*.h"))
     out: dict[str, Path] = {}
 
     # --- product library ---------------------------------------------------
@@ -165,13 +165,14 @@ def build(force: bool = False, verbose: bool = False) -> dict[str, Path]:
              (CSRC / "demod_kernel_lat.hip", "demod_kernel_lat", ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
              (CSRC / "demod_aux.hip", "demod_aux", []), (CSRC / "recording.hip", "recording", []),
              (CSRC / "demod_api.cpp", "demod_api", []), (CSRC / "host_pipe.cpp", "host_pipe", []),
-             (CSRC / "demod_host.cpp", "demod_host", [])]
+             (CSRC / "demod_host.cpp", "demod_host", []),
+             (CSRC / "frontend.hip", "frontend", []), (CSRC / "frontend_design.cpp", "frontend_design", [])]
     # the assembly of the rotating register window is generated (csrc/gen_rotwin_asm.py -> csrc/rotwin_asm.h)
     for gen, inc in ((CSRC / "gen_rotwin_asm.py", CSRC / "rotwin_asm.h"), (CSRC / "gen_rotpk_asm.py", CSRC / "rotpk_asm.h")):
         if force or _stale(inc, [gen]):
             text = subprocess.run([sys.executable, str(gen)], capture_output=True, text=True, check=True).stdout
             inc.write_text(text)
-            headers = sorted(CSRC.glob("*.h")) + [ROOT / "include" / "meteor_demod_amd.h"]
+            headers = sorted(CSRC.glob("*.h")) + sorted((ROOT / "include").glob("*.h"))
     objs = []
     asm_units = {"demod_kernel_rot": LIB / "demod_kernel_rot.gfx950.s", "demod_kernel_rotp": LIB / "demod_kernel_rotp.gfx950.s"}
     checked = LIB / "asm_partition.ok"
@@ -223,7 +224,7 @@ def build(force: bool = False, verbose: bool = False) -> dict[str, Path]:
     if host_src.exists():
         exe = LIB / "meteor_demod_amd"
         tui_src = [ROOT / "host" / "tui.c", ROOT / "host" / "tui.h"]
-        if force or _stale(exe, [host_src, ROOT / "include" / "meteor_demod_amd.h", so, *tui_src]):
+        if force or _stale(exe, [host_src, *sorted((ROOT / "include").glob("*.h")), so, *tui_src]):
             cc = shutil.which("gcc") or shutil.which("cc")
             # the full-screen display needs ncurses (as the reference's ENABLE_TUI does); linked statically so that the binary
             # that travels to another box of this image needs nothing beyond libc there
