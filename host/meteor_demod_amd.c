@@ -27,6 +27,10 @@
  * is moved from <Hz> off the recording's centre to 0 Hz, filtered and decimated on the GPU, and demodulated at fs / N.  -s / --bps
  * (or the WAV header) describe the recording as always.  Its entries are weak references: this program still links against a
  * library without them (and says so when asked for the front end).
+ * --offset auto surveys each input file first (include/meteor_demod_amd_survey.h: spectrum of the whole file, candidates
+ * confirmed by their symbol-rate line) and uses the first confirmed signal's offset - each file of a batch its own; no confirmed
+ * signal is exit 1 before any output file exists.  --decimate auto takes the largest N the front end accepts; --scan prints the
+ * candidates and exits.  Weak references as well.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -44,6 +48,7 @@
 
 #include "meteor_demod_amd.h"
 #include "meteor_demod_amd_frontend.h"
+#include "meteor_demod_amd_survey.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
 #endif
@@ -75,7 +80,7 @@ static const struct option longopts[] = {
 	{ "device", 1, NULL, 0x01 },    { "tiled", 0, NULL, 0x02 },   { "tile-samples", 1, NULL, 0x03 },
 	{ "pilot-margin", 1, NULL, 0x04 }, { "carrier-seed", 1, NULL, 0x05 }, { "devices", 1, NULL, 0x06 }, { "plan", 0, NULL, 0x07 },
 	{ "tui-selftest", 0, NULL, 0x08 }, { "tui", 0, NULL, 0x09 }, { "jobs", 1, NULL, 0x0a },
-	{ "offset", 1, NULL, 0x0b },    { "decimate", 1, NULL, 0x0c },
+	{ "offset", 1, NULL, 0x0b },    { "decimate", 1, NULL, 0x0c }, { "scan", 0, NULL, 0x0d },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -92,6 +97,17 @@ have_frontend(void)
 {
 	return mdemod_fe_design && mdemod_fe_create && mdemod_fe_destroy && mdemod_fe_demodulator && mdemod_fe_process_host &&
 	       mdemod_fe_demodulate_recording_host;
+}
+
+/* the survey's entries (include/meteor_demod_amd_survey.h: --offset auto, --decimate auto, --scan): weak as well */
+#pragma weak mdemod_survey_default_opts
+#pragma weak mdemod_survey_plan
+#pragma weak mdemod_survey_host
+
+static int
+have_survey(void)
+{
+	return mdemod_survey_default_opts && mdemod_survey_plan && mdemod_survey_host;
 }
 
 /* --offset: a signed number of Hz with an optional k / M suffix (fractions kept); 1 on a malformed one */
@@ -153,6 +169,14 @@ usage(const char *prog)
 	        "       --decimate <n>      The front end low-pass filters and keeps every n-th sample (1..128; the sample\n"
 	        "                           rate must be a multiple of n, and rate / n at least 2.4 x the symbol rate); the\n"
 	        "                           demodulator runs at rate / n.  Either option turns the front end on\n"
+	        "       --offset auto       Survey each input file first (spectrum of the whole file on the GPU, candidates\n"
+	        "                           confirmed by their symbol-rate line) and use the offset of the first confirmed\n"
+	        "                           signal; exit 1, without an output file, when none is confirmed.  Not on stdin\n"
+	        "       --decimate auto     The largest n the front end accepts for this sample and symbol rate (implied by\n"
+	        "                           --offset auto when --decimate is absent)\n"
+	        "       --scan              Survey only: one line per candidate of each file on stdout,\n"
+	        "                           offset_hz psd_snr_db clock_quality carrier_quality confirmed\n"
+	        "                           (confirmed ones first, then by psd_snr_db), and exit 0 without demodulating\n"
 	        "   -h, --help   -v, --version\n", prog);
 }
 
@@ -292,6 +316,7 @@ struct worker {
 	int         jobs;                    /* --tiled: files of this worker in flight at once */
 	int         use_fe;                  /* --offset / --decimate: the front end ahead of the demodulator */
 	mdemod_fe_params fe;
+	double     *fe_offsets;              /* --offset auto: one offset per file of this worker (NULL: fe.offset_hz for all) */
 	int         rc;                      /* exit code of this worker: 0 ok, 1 host error, 2 library error */
 };
 
@@ -328,6 +353,8 @@ tiled_one_file(struct worker *w, int f)
 	const float symrate = (float)w->p.symrate;
 	const int tile_samples = w->tile_samples, pilot_margin = w->pilot_margin, carrier_seed = w->carrier_seed;
 	mdemod_params p = w->p;
+	mdemod_fe_params fe_one = w->fe;
+	if (w->fe_offsets) { fe_one.offset_hz = w->fe_offsets[f]; fe_one.offsets_hz = NULL; }
 	const int timing = getenv("MDEMOD_CLI_TIMING") != NULL;       /* where the wall time of a --tiled run goes (stderr) */
 	const double t_begin = now_ms();
 	size_t cap_bytes = 1u << 26, len = 0;
@@ -363,7 +390,7 @@ tiled_one_file(struct worker *w, int f)
 	if (carrier_seed >= 0) ro.carrier_seed = (uint32_t)carrier_seed;
 	mdemod_recording_report rr;
 	const double t_read = now_ms();
-	int rc2 = w->use_fe ? mdemod_fe_demodulate_recording_host(&p, &w->fe, &ro, data, n_samples, soft_all, cap_sym, &rr)
+	int rc2 = w->use_fe ? mdemod_fe_demodulate_recording_host(&p, &fe_one, &ro, data, n_samples, soft_all, cap_sym, &rr)
 	                    : mdemod_demodulate_recording_host(&p, &ro, data, n_samples, soft_all, cap_sym, &rr);
 	const double t_lib = now_ms();
 	if (rc2 != MDEMOD_OK) {
@@ -533,7 +560,7 @@ run_exact(struct worker *w)
 			/* main.c:249-261: status line from the snapshot of stream 0, at most once per refresh period */
 			last_status = now_ms();
 			/* with the front end: the carrier from the recording's centre (offset + the PLL's estimate), the clock at fs / D */
-			const double freq_hz = st[0].pll_freq * symrate / (2 * M_PI) * (oqpsk ? 2 : 1) + (fe ? w->fe.offset_hz : 0.0);
+			const double freq_hz = st[0].pll_freq * symrate / (2 * M_PI) * (oqpsk ? 2 : 1) + (fe ? (w->fe_offsets ? w->fe_offsets[0] : w->fe.offset_hz) : 0.0);
 			const double rate_hz = st[0].omega * ((double)(samplerate / D) * interp) / (2 * M_PI);
 			const long pos = io[0].in != stdin ? ftell(io[0].in) : 0;
 #ifdef MDEMOD_TUI
@@ -606,6 +633,36 @@ parse_devices(const char *s, int *out, int cap)
 
 #define MAX_DEVICES 64
 
+/* the offset as --scan prints it (0.1 Hz): --offset auto uses the same number, so --offset <what --scan printed> is the same run */
+static double
+round_offset(double hz)
+{
+	char buf[64];
+	snprintf(buf, sizeof buf, "%.1f", hz);
+	return strtod(buf, NULL);
+}
+
+/* The survey of one input file: its samples from where the header ended to the end of the file, read whole, and the file put back
+ * where it was.  0, 1 (a host error, already reported) or the library's code (< 0). */
+static int
+survey_file(const mdemod_params *in, const mdemod_survey_opts *so, struct stream_io *io, mdemod_survey_hit *hits, uint32_t *n_hits)
+{
+	const long here = ftell(io->in);
+	if (here < 0 || fseek(io->in, 0, SEEK_END)) { fprintf(stderr, "%s: cannot look ahead in this input (not a regular file)\n", io->in_name); return 1; }
+	const long end = ftell(io->in);
+	if (end < here || fseek(io->in, here, SEEK_SET)) { fprintf(stderr, "%s: cannot look ahead in this input\n", io->in_name); return 1; }
+	const size_t len = (size_t)(end - here), sb = 2 * (size_t)in->bps / 8;
+	unsigned char *data = malloc(len ? len : 1);
+	if (!data) { fprintf(stderr, "out of memory reading %s\n", io->in_name); return 1; }
+	const size_t got = fread(data, 1, len, io->in);
+	int rc = 1;
+	if (fseek(io->in, here, SEEK_SET)) fprintf(stderr, "%s: cannot look ahead in this input\n", io->in_name);
+	else rc = mdemod_survey_host(in, so, data, got / sb, hits, MDEMOD_SURVEY_MAX_CANDIDATES, n_hits);
+	free(data);
+	if (*n_hits > MDEMOD_SURVEY_MAX_CANDIDATES) *n_hits = MDEMOD_SURVEY_MAX_CANDIDATES;
+	return rc;
+}
+
 int
 main(int argc, char **argv)
 {
@@ -617,6 +674,8 @@ main(int argc, char **argv)
 	int devs[MAX_DEVICES], n_dev = 0, plan = 0, jobs = 4;
 	int use_fe = 0, decimation = 1;
 	double offset_hz = 0.0;
+	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0;
+	double *auto_offsets = NULL;               /* --offset auto: the offset chosen for each file */
 #ifdef MDEMOD_TUI
 	int force_tui = 0;
 #endif
@@ -637,15 +696,20 @@ main(int argc, char **argv)
 		case 0x09: break;                             /* --tui in a build without the display: accepted, nothing to draw */
 #endif
 		case 0x0a: jobs = atoi(optarg); if (jobs < 1) { fprintf(stderr, "--jobs: a positive number\n"); return 1; } break;
+		case 0x0d: scan = 1; break;
 		case 0x0b:
+			if (!strcmp(optarg, "auto")) { auto_offset = 1; use_fe = 1; break; }
+			auto_offset = 0;
 			if (parse_hz(optarg, &offset_hz)) { fprintf(stderr, "--offset: a number of Hz (k/M suffixes), e.g. 300k or -1.2M\n"); return 1; }
 			use_fe = 1;
 			break;
 		case 0x0c: {
 			char *end;
+			if (!strcmp(optarg, "auto")) { auto_decimate = 1; decimate_given = 0; use_fe = 1; break; }
 			const long v = strtol(optarg, &end, 10);
-			if (end == optarg || *end || v < 1 || v > 1 << 20) { fprintf(stderr, "--decimate: a positive integer\n"); return 1; }
+			if (end == optarg || *end || v < 1 || v > 1 << 20) { fprintf(stderr, "--decimate: a positive integer, or auto\n"); return 1; }
 			decimation = (int)v;
+			auto_decimate = 0; decimate_given = 1;
 			use_fe = 1;
 			break;
 		}
@@ -695,6 +759,13 @@ main(int argc, char **argv)
 		fprintf(stderr, "--offset / --decimate: this library has no front end (built without include/meteor_demod_amd_frontend.h's entries)\n");
 		return 1;
 	}
+	if ((auto_offset || auto_decimate || scan) && !have_survey()) {
+		fprintf(stderr, "--offset auto / --decimate auto / --scan: this library has no survey (built without include/meteor_demod_amd_survey.h's entries)\n");
+		return 1;
+	}
+	if (auto_offset || scan)
+		for (int i = optind; i < argc; i++)
+			if (!strcmp(argv[i], "-")) { fprintf(stderr, "--offset auto / --scan: not on stdin (there is nothing to look ahead in): give the offset with --offset <hz>\n"); return 1; }
 	if (plan) {
 		/* the sharding arithmetic, without touching files or GPUs: file i on the (i mod G)-th device of the list */
 		if (!n_dev) { fprintf(stderr, "--plan needs --devices\n"); return 1; }
@@ -713,8 +784,9 @@ main(int argc, char **argv)
 	/* every way out from here on: files closed, nothing left allocated (the sanitizer builds of tests/test_sanitize.py look) */
 #define LEAVE(code) do { \
 		close_all(io, n_files); \
-		for (int d_ = 0; d_ < n_workers; d_++) { free(ws[d_].io); } \
+		for (int d_ = 0; d_ < n_workers; d_++) { free(ws[d_].io); free(ws[d_].fe_offsets); } \
 		free(ws); \
+		free(auto_offsets); \
 		for (int i_ = 0; i_ < n_files; i_++) { free(io[i_].out_name); } \
 		free(io); \
 		return (code); \
@@ -742,6 +814,52 @@ main(int argc, char **argv)
 	mdemod_fe_params fep;
 	memset(&fep, 0, sizeof(fep));
 	fep.offset_hz = offset_hz; fep.decimation = decimation; fep.taps_per_phase = 0;
+	if ((auto_offset || auto_decimate || scan) && bps_ok) {
+		/* the survey: before any output file exists, so that a file without a signal leaves nothing behind */
+		mdemod_params in;
+		memset(&in, 0, sizeof(in));
+		in.pll_bw = pll_bw; in.sym_bw = MDEMOD_DEFAULT_SYM_BW; in.samplerate = samplerate; in.symrate = (int)symrate;
+		in.interp_factor = interp; in.rrc_order = rrc_order; in.oqpsk = oqpsk; in.freq_max = freq_max_delta;
+		in.bps = bps; in.device = n_dev ? devs[0] : device; in.n_streams = 1;
+		if (auto_decimate || (!decimate_given && (auto_offset || scan))) {
+			const int rc = mdemod_survey_plan(&in, NULL, &decimation);
+			if (rc != MDEMOD_OK) { fprintf(stderr, "--decimate auto: %s\n", why_of(rc)); LEAVE(1); }
+			fep.decimation = decimation;
+		}
+		if (auto_offset || scan) {
+			mdemod_survey_opts so;
+			mdemod_survey_default_opts(&so);
+			so.decimation = decimation;
+			auto_offsets = calloc((size_t)n_files, sizeof(*auto_offsets));
+			if (!auto_offsets) LEAVE(1);
+			for (int i = 0; i < n_files; i++) {
+				mdemod_survey_hit hits[MDEMOD_SURVEY_MAX_CANDIDATES];
+				uint32_t n_hits = 0;
+				const int rc = survey_file(&in, &so, &io[i], hits, &n_hits);
+				if (rc == 1) LEAVE(1);
+				if (rc) { fprintf(stderr, "%s: survey: %s\n", io[i].in_name, why_of(rc)); LEAVE(2); }
+				if (scan) {
+					if (n_files > 1) printf("# %s\n", io[i].in_name);
+					for (uint32_t k = 0; k < n_hits; k++)
+						printf("%.1f %.2f %.2f %.2f %d\n", round_offset(hits[k].offset_hz), hits[k].psd_snr_db, hits[k].clock_quality,
+						       hits[k].carrier_quality, hits[k].confirmed);
+					continue;
+				}
+				if (!n_hits || !hits[0].confirmed) {             /* (confirmed hits come first) */
+					if (n_hits)
+						fprintf(stderr, "%s: no LRPT signal of %d sym/s confirmed; the best candidate, at %+.1f Hz (%.1f dB over the floor), has a "
+						        "symbol-rate line of quality %.1f\n", io[i].in_name, (int)symrate, hits[0].offset_hz, hits[0].psd_snr_db, hits[0].clock_quality);
+					else
+						fprintf(stderr, "%s: no LRPT signal of %d sym/s found: nothing stands out of the noise floor\n", io[i].in_name, (int)symrate);
+					LEAVE(1);
+				}
+				auto_offsets[i] = round_offset(hits[0].offset_hz);
+			}
+			if (scan) LEAVE(0);
+			fep.offset_hz = auto_offsets[0];
+		}
+	}
+	if (scan) LEAVE(0);
 	if (use_fe && bps_ok) {
 		/* the front end's settings are checked on the host, before any output file or the GPU: a refusal leaves nothing behind */
 		mdemod_params in;
@@ -777,6 +895,8 @@ main(int argc, char **argv)
 #endif
 	if (!quiet)                                                                        /* main.c:200 */
 		for (int i = 0; i < n_files; i++) say("Input: %s, output: %s\n", io[i].in_name, stdout_mode ? "(stdout)" : io[i].out_name);
+	if (!quiet && auto_offsets)                                                        /* (the display's log when it is up: the chosen offset stays on screen) */
+		for (int i = 0; i < n_files; i++) say("%s: LRPT found %+.1f Hz from the centre, front end /%d\n", io[i].in_name, auto_offsets[i], decimation);
 	if (!bps_ok) {
 		LEAVE(0);
 	}
@@ -819,6 +939,14 @@ main(int argc, char **argv)
 		w->io = calloc((size_t)w->n_files, sizeof(*w->io));
 		if (!w->io) LEAVE(1);
 		for (int i = d, k = 0; i < n_files; i += n_dev, k++) w->io[k] = io[i];
+		if (auto_offsets && n_files > 1) {
+			/* each file its own offset: the worker's share of the list, in the order of its streams */
+			w->fe_offsets = calloc((size_t)w->n_files, sizeof(double));
+			if (!w->fe_offsets) LEAVE(1);
+			for (int i = d, k = 0; i < n_files; i += n_dev, k++) w->fe_offsets[k] = auto_offsets[i];
+			w->fe.offset_hz = w->fe_offsets[0];
+			w->fe.offsets_hz = w->fe_offsets;
+		}
 		w->p.n_streams = (uint32_t)w->n_files;
 	}
 	if (n_dev == 1) {

@@ -7,6 +7,9 @@ interface (demod.py).  Nothing here computes on the CPU.
 """
 from .demod import DemodConfig, Demodulator, derive_tables, scale_freq_max  # noqa: F401
 from .frontend import FrontEnd, FrontEndConfig, demodulate_recording_frontend, design_taps  # noqa: F401
+from . import survey  # noqa: F401
+from .survey import Hit, survey_plan  # noqa: F401
 
 __all__ = ["DemodConfig", "Demodulator", "derive_tables", "scale_freq_max",
-           "FrontEnd", "FrontEndConfig", "demodulate_recording_frontend", "design_taps"]
+           "FrontEnd", "FrontEndConfig", "demodulate_recording_frontend", "design_taps",
+           "survey", "Hit", "survey_plan"]
