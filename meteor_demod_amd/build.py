@@ -205,8 +205,6 @@ def build(force: bool = False, verbose: bool = False) -> dict[str, Path]:
             raise RuntimeError("register partition of the v3 kernels violated (compiler code in the assembly's registers, or scratch "
                                "where there must be none):\n  " + "\n  ".join(bad[:20]))
         checked.write_text("ok\n")
-    for stale in LIB.glob("demod_kernel_rw_*.o"):            # objects of the v2 kernel (retired in round 4) from an older tree
-        stale.unlink()
     so = LIB / "libmeteor_demod_amd.so"
     if force or _stale(so, objs):
         _run([hipcc, "-shared", "-fPIC", "-pthread", f"--offload-arch={ARCH}", "-o", str(so), *map(str, objs)])

@@ -15,6 +15,7 @@
 
 #include "demod_host.h"
 #include "demod_internal.h"
+#include "hip_host.h"
 
 struct mdemod_ctx {
 	mdemod_params params;
@@ -34,34 +35,12 @@ struct mdemod_ctx {
 	bool          lat_ok;      /* the latency kernel (one stream per wave) fits this configuration */
 	int           lat_ring, lat_span;
 	size_t        lat_lds;
-	std::vector<void *> allocs;
+	MdmDevMem     mem;
 
 	void   *pipe;      /* host_pipe.cpp: pinned staging, streams, events of mdemod_process_host (grow only) */
 };
 
 namespace {
-
-#define HIP_TRY(expr)                                                                   \
-	do {                                                                                \
-		hipError_t e_ = (expr);                                                         \
-		if (e_ != hipSuccess) {                                                         \
-			mdm_note_error("%s failed: %s (%s:%d)", #expr,                           \
-			        hipGetErrorString(e_), __FILE__, __LINE__);                         \
-			(void)hipGetLastError();   /* reported: it must not be read again as the status of somebody's next launch */ \
-			return e_ == hipErrorOutOfMemory ? MDEMOD_ERR_NOMEM : MDEMOD_ERR_HIP;       \
-		}                                                                               \
-	} while (0)
-
-template <typename T>
-int
-dev_alloc(mdemod_ctx *ctx, T **ptr, size_t count)
-{
-	void *p = nullptr;
-	HIP_TRY(hipMalloc(&p, count * sizeof(T) + 16));
-	ctx->allocs.push_back(p);
-	*ptr = static_cast<T *>(p);
-	return MDEMOD_OK;
-}
 
 template <typename T>
 int
@@ -97,18 +76,6 @@ wants_latency_kernel(const mdemod_ctx *ctx)
 }
 
 int
-select_device(const mdemod_ctx *ctx)
-{
-	/* Every device entry begins here.  The launch wrappers report hipGetLastError() after their launch: an error some EARLIER call of
-	 * this thread left behind (the caller's own, another library's, a refused hipSetDevice) would come back as the status of a launch
-	 * that went through (r06: a context made right after mdemod_create had refused a device that does not exist failed in
-	 * mdemod_launch_reset with that device's error).  A launch's status is the launch's: what is pending is dropped first. */
-	(void)hipGetLastError();
-	HIP_TRY(hipSetDevice(ctx->params.device));
-	return MDEMOD_OK;
-}
-
-int
 launch(mdemod_ctx *ctx, DemodLaunch &L, hipStream_t stream)
 {
 	L.c = ctx->tab.c;
@@ -136,6 +103,37 @@ launch(mdemod_ctx *ctx, DemodLaunch &L, hipStream_t stream)
 		return MDEMOD_ERR_PARAM;                      /* (cannot happen: every register-window plan is one of the v3 kernels above) */
 	else
 		HIP_TRY(mdemod_launch_demod(L, ctx->params.bps, ctx->block_threads, ctx->v1_global_table ? 1 : 0, ctx->lds_bytes, stream));
+	return MDEMOD_OK;
+}
+
+/* mdemod_create: the tables and the power-on state, on a private stream that is waited for */
+int
+upload_tables(mdemod_ctx *ctx)
+{
+	MdmStream own;
+	HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+	HIP_TRY(hipMemcpyAsync(ctx->d_ctab, ctx->tab.ctab.data(), ctx->tab.ctab.size() * sizeof(float), hipMemcpyHostToDevice, own.s));
+	HIP_TRY(hipMemcpyAsync(ctx->d_rrc, ctx->tab.rrc.data(), ctx->tab.rrc.size() * sizeof(float), hipMemcpyHostToDevice, own.s));
+	HIP_TRY(hipMemcpyAsync(ctx->d_lut, ctx->tab.tanh_lut, sizeof(ctx->tab.tanh_lut), hipMemcpyHostToDevice, own.s));
+	const int rc = mdemod_reset(ctx, own.s);
+	if (rc) return rc;
+	HIP_TRY(hipStreamSynchronize(own.s));
+	return MDEMOD_OK;
+}
+
+/* a self-test that counts on the device: zeroed counters, the launch, the counters back */
+template <size_t N, typename Launch>
+int
+selftest_count(mdemod_ctx *ctx, unsigned long long (&h)[N], Launch launch)
+{
+	int rc = mdm_select_device(ctx->params.device);
+	if (rc) return rc;
+	MdmDevMem mem;
+	unsigned long long *d = nullptr;
+	if ((rc = mem.alloc(&d, N))) return rc;
+	HIP_TRY(hipMemset(d, 0, sizeof(h)));
+	HIP_TRY(launch(d));
+	HIP_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
 	return MDEMOD_OK;
 }
 
@@ -236,15 +234,15 @@ mdemod_abi_version(void)
 int
 mdemod_init_device(int device)
 try { MDEMOD_API_ENTER
-	(void)hipGetLastError();                                               /* (see select_device) */
-	HIP_TRY(hipSetDevice(device));
+	int rc = mdm_select_device(device);
+	if (rc) return rc;
 	HIP_TRY(hipFree(nullptr));                                             /* forces the context */
 	/* ... and the code objects (loaded at the first launch of a process), on a stream of its own */
-	hipStream_t s = nullptr;
-	HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-	const bool ok = mdemod_launch_warm(s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-	(void)hipStreamDestroy(s);
-	return ok ? MDEMOD_OK : MDEMOD_ERR_HIP;
+	MdmStream own;
+	HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+	HIP_TRY(mdemod_launch_warm(own.s));
+	HIP_TRY(hipStreamSynchronize(own.s));
+	return MDEMOD_OK;
 } MDEMOD_API_CATCH
 
 int
@@ -303,54 +301,28 @@ mdemod_create(const mdemod_params *params, mdemod_ctx **out)
 	int rc = plan_context(ctx);
 	if (rc) { delete ctx; return rc; }
 	DemodConsts &c = ctx->tab.c;
+	rc = mdm_select_device(params->device);
+	if (rc) { delete ctx; return rc; }
 
 #define CREATE_TRY(expr) do { rc = (expr); if (rc) { mdemod_destroy(ctx); return rc; } } while (0)
-	{
-		(void)hipGetLastError();                       /* (see select_device) */
-		hipError_t e = hipSetDevice(params->device);
-		if (e != hipSuccess) {
-			mdm_note_error("no usable HIP device %d: %s", params->device, hipGetErrorString(e));
-			(void)hipGetLastError();
-			delete ctx;
-			return MDEMOD_ERR_HIP;
-		}
-	}
 	const size_t n = params->n_streams;
 	DemodStateSoA &s = ctx->st;
-	CREATE_TRY(dev_alloc(ctx, &s.agc_gain, n));   CREATE_TRY(dev_alloc(ctx, &s.agc_bias_re, n));
-	CREATE_TRY(dev_alloc(ctx, &s.agc_bias_im, n)); CREATE_TRY(dev_alloc(ctx, &s.pll_phase, n));
-	CREATE_TRY(dev_alloc(ctx, &s.pll_freq, n));   CREATE_TRY(dev_alloc(ctx, &s.pll_err, n));
-	CREATE_TRY(dev_alloc(ctx, &s.t_phase, n));    CREATE_TRY(dev_alloc(ctx, &s.t_freq, n));
-	CREATE_TRY(dev_alloc(ctx, &s.t_prev, n));     CREATE_TRY(dev_alloc(ctx, &s.inphase, n));
-	CREATE_TRY(dev_alloc(ctx, &s.flags, n));
-	CREATE_TRY(dev_alloc(ctx, &s.n_samples, n));  CREATE_TRY(dev_alloc(ctx, &s.n_symbols, n));
-	CREATE_TRY(dev_alloc(ctx, &s.first_lock, n));
-	CREATE_TRY(dev_alloc(ctx, &s.sym_this_call, n)); CREATE_TRY(dev_alloc(ctx, &s.ev_this_call, n));
-	CREATE_TRY(dev_alloc(ctx, &s.overflow, n));
+#define X(field) CREATE_TRY(ctx->mem.alloc(&s.field, n));
+	MDEMOD_STATE_ARRAYS(X)
+#undef X
 	{
 		unsigned char *h = nullptr;
-		CREATE_TRY(dev_alloc(ctx, &h, static_cast<size_t>(c.hpad) * n * (ctx->tab.use_rw ? 8 : ctx->sample_bytes)));
+		CREATE_TRY(ctx->mem.alloc(&h, static_cast<size_t>(c.hpad) * n * (ctx->tab.use_rw ? 8 : ctx->sample_bytes)));
 		s.hist = h;
 	}
-	CREATE_TRY(dev_alloc(ctx, &s.events, n * MDEMOD_MAX_LOCK_EVENTS));
-	CREATE_TRY(dev_alloc(ctx, &ctx->d_ctab, ctx->tab.ctab.size()));
-	CREATE_TRY(dev_alloc(ctx, &ctx->d_lut, 32));
-	CREATE_TRY(dev_alloc(ctx, &ctx->d_rrc, ctx->tab.rrc.size()));
-	{
-		/* tables and the power-on state go in on a stream of their own, and only that stream is waited for: a context made while
-		   other contexts run (a second host thread, a recording's tile bank next to its serial head) must not wait for their
-		   kernels, which hipDeviceSynchronize and the null stream's copies did */
-		hipStream_t s0 = nullptr;
-		hipError_t e = hipStreamCreateWithFlags(&s0, hipStreamNonBlocking);
-		if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_ctab, ctx->tab.ctab.data(), ctx->tab.ctab.size() * sizeof(float), hipMemcpyHostToDevice, s0);
-		if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_rrc, ctx->tab.rrc.data(), ctx->tab.rrc.size() * sizeof(float), hipMemcpyHostToDevice, s0);
-		if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_lut, ctx->tab.tanh_lut, sizeof(ctx->tab.tanh_lut), hipMemcpyHostToDevice, s0);
-		int rc_reset = MDEMOD_OK;
-		if (e == hipSuccess) rc_reset = mdemod_reset(ctx, s0);
-		if (e == hipSuccess) e = hipStreamSynchronize(s0);
-		if (s0) (void)hipStreamDestroy(s0);
-		if (e != hipSuccess || rc_reset != MDEMOD_OK) { mdemod_destroy(ctx); return rc_reset != MDEMOD_OK ? rc_reset : MDEMOD_ERR_HIP; }
-	}
+	CREATE_TRY(ctx->mem.alloc(&s.events, n * MDEMOD_MAX_LOCK_EVENTS));
+	CREATE_TRY(ctx->mem.alloc(&ctx->d_ctab, ctx->tab.ctab.size()));
+	CREATE_TRY(ctx->mem.alloc(&ctx->d_lut, 32));
+	CREATE_TRY(ctx->mem.alloc(&ctx->d_rrc, ctx->tab.rrc.size()));
+	/* tables and the power-on state go in on a stream of their own, and only that stream is waited for: a context made while
+	   other contexts run (a second host thread, a recording's tile bank next to its serial head) must not wait for their
+	   kernels, which hipDeviceSynchronize and the null stream's copies did */
+	CREATE_TRY(upload_tables(ctx));
 #undef CREATE_TRY
 	} catch (...) {                                    /* (see MDEMOD_API_CATCH; what the context holds so far is given back) */
 		mdm_note_error("mdemod_create: a C++ exception reached the boundary (allocation failed)");
@@ -366,16 +338,15 @@ mdemod_destroy(mdemod_ctx *ctx)
 {
 	if (!ctx) return;
 	(void)hipSetDevice(ctx->params.device);
-	for (void *p : ctx->allocs) (void)hipFree(p);
 	mdemod_hostpipe_free(ctx->pipe);
-	delete ctx;
+	delete ctx;                                        /* (with everything ctx->mem holds) */
 }
 
 int
 mdemod_reset(mdemod_ctx *ctx, void *hip_stream)
 try { MDEMOD_API_ENTER
 	if (!ctx) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	HIP_TRY(hipMemsetAsync(ctx->st.events, 0, sizeof(mdemod_lock_event) * MDEMOD_MAX_LOCK_EVENTS * ctx->params.n_streams,
 	                       static_cast<hipStream_t>(hip_stream)));
@@ -402,7 +373,7 @@ try { MDEMOD_API_ENTER
 	if (!ctx || (!iq_dev && n_samples) || !soft_dev) return MDEMOD_ERR_PARAM;
 	if (n_samples > 0x3FFFFF00u) return MDEMOD_ERR_PARAM;
 	if (soft_cap_symbols > soft_stride_symbols) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	DemodLaunch L;
 	memset(&L, 0, sizeof(L));
@@ -418,7 +389,7 @@ mdemod_process_device(mdemod_ctx *ctx, const void *iq_dev, const uint64_t *iq_of
 try { MDEMOD_API_ENTER
 	if (!ctx || !iq_dev || !iq_offset_dev || !n_samples_dev || !soft_dev) return MDEMOD_ERR_PARAM;
 	if (soft_cap_symbols > soft_stride_symbols) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	DemodLaunch L;
 	memset(&L, 0, sizeof(L));
@@ -432,7 +403,7 @@ mdemod_process_host(mdemod_ctx *ctx, const void *const *iq_host, const uint32_t 
                     int8_t *const *soft_host, const uint32_t *soft_cap, uint32_t *n_symbols)
 try { MDEMOD_API_ENTER
 	if (!ctx || !iq_host || !n_samples || !soft_host || !soft_cap) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	/* other work of this context (e.g. an asynchronous reset on the caller's stream) must be through before the
 	 * pipeline's own streams touch the state */
@@ -445,7 +416,7 @@ int
 mdemod_pin_host_buffer(mdemod_ctx *ctx, const void *base, size_t bytes)
 try { MDEMOD_API_ENTER
 	if (!ctx || !base || !bytes) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	return mdemod_hostpipe_pin(&ctx->pipe, base, bytes);
 } MDEMOD_API_CATCH
@@ -454,7 +425,7 @@ int
 mdemod_unpin_host_buffer(mdemod_ctx *ctx, const void *base)
 try { MDEMOD_API_ENTER
 	if (!ctx || !base) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	return mdemod_hostpipe_unpin(ctx->pipe, base);
 } MDEMOD_API_CATCH
@@ -468,7 +439,7 @@ try { MDEMOD_API_ENTER
 	if (!ctx || !out) return MDEMOD_ERR_PARAM;
 	if (static_cast<uint64_t>(first) + count > ctx->params.n_streams) return MDEMOD_ERR_RANGE;
 	if (!count) return MDEMOD_OK;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	hipStream_t st = static_cast<hipStream_t>(hip_stream);
 	const DemodStateSoA &s = ctx->st;
@@ -503,7 +474,7 @@ mdemod_get_lock_events(mdemod_ctx *ctx, uint32_t stream, mdemod_lock_event *out,
 try { MDEMOD_API_ENTER
 	if (!ctx || !n) return MDEMOD_ERR_PARAM;
 	if (stream >= ctx->params.n_streams) return MDEMOD_ERR_RANGE;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	hipStream_t st = static_cast<hipStream_t>(hip_stream);
 	uint32_t cnt = 0;
@@ -530,7 +501,7 @@ mdemod_get_state(mdemod_ctx *ctx, uint32_t stream, mdemod_stream_state *out, voi
 try { MDEMOD_API_ENTER
 	if (!ctx || !out) return MDEMOD_ERR_PARAM;
 	if (stream >= ctx->params.n_streams) return MDEMOD_ERR_RANGE;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	hipStream_t st = static_cast<hipStream_t>(hip_stream);
 	int32_t flags = 0;
@@ -588,7 +559,7 @@ try { MDEMOD_API_ENTER
 	if (stream >= ctx->params.n_streams) return MDEMOD_ERR_RANGE;
 	if (in->t_dual_state != 1 && in->t_dual_state != 2) return MDEMOD_ERR_PARAM;
 	if (!carrier_in_domain(*in) || !clock_in_domain(ctx, *in)) { note_domain(ctx, *in); return MDEMOD_ERR_PARAM; }
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	hipStream_t st = static_cast<hipStream_t>(hip_stream);
 	mdemod_stream_state v = *in;
@@ -610,7 +581,7 @@ try { MDEMOD_API_ENTER
 	if (!ctx || !seed) return MDEMOD_ERR_PARAM;
 	if (seed->t_dual_state != 1 && seed->t_dual_state != 2) return MDEMOD_ERR_PARAM;
 	if (!carrier_in_domain(*seed) || !clock_in_domain(ctx, *seed)) { note_domain(ctx, *seed); return MDEMOD_ERR_PARAM; }
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	const int32_t flags = (seed->pll_locked ? MDEMOD_FLAG_LOCKED : 0) | (seed->pll_locked_once ? MDEMOD_FLAG_LOCKED_ONCE : 0) |
 	                      (seed->pll_updown > 0 ? MDEMOD_FLAG_UPDOWN_POS : 0) | (seed->t_dual_state << MDEMOD_FLAG_DUAL_SHIFT);
@@ -623,7 +594,7 @@ int
 mdemod_rotate_carrier(mdemod_ctx *ctx, const int32_t *quarter_turns_dev, void *hip_stream)
 try { MDEMOD_API_ENTER
 	if (!ctx || !quarter_turns_dev) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	HIP_TRY(mdemod_launch_rotate(ctx->st, quarter_turns_dev, ctx->params.n_streams, ctx->params.oqpsk ? 1 : 0, static_cast<hipStream_t>(hip_stream)));
 	return MDEMOD_OK;
@@ -633,7 +604,7 @@ int
 mdemod_set_carrier_seeds(mdemod_ctx *ctx, const float *freq_dev, const int32_t *updown_dev, void *hip_stream)
 try { MDEMOD_API_ENTER
 	if (!ctx || !freq_dev || !updown_dev) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	HIP_TRY(mdemod_launch_carrier_seeds(ctx->st, freq_dev, updown_dev, ctx->params.n_streams, static_cast<hipStream_t>(hip_stream)));
 	return MDEMOD_OK;
@@ -643,7 +614,7 @@ int
 mdemod_set_gain_seeds(mdemod_ctx *ctx, const float *gain_dev, void *hip_stream)
 try { MDEMOD_API_ENTER
 	if (!ctx || !gain_dev) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	HIP_TRY(mdemod_launch_gain_seeds(ctx->st, gain_dev, ctx->params.n_streams, static_cast<hipStream_t>(hip_stream)));
 	return MDEMOD_OK;
@@ -653,7 +624,7 @@ int
 mdemod_set_clock_seeds(mdemod_ctx *ctx, const float *t_freq_dev, void *hip_stream)
 try { MDEMOD_API_ENTER
 	if (!ctx || !t_freq_dev) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	/* clamped on the way in to the words the reference's loop can hold (clock_in_domain above: what mdemod_set_state refuses) */
 	const DemodConsts &c = ctx->tab.c;
@@ -669,7 +640,7 @@ try { MDEMOD_API_ENTER
 	if (!ctx || !out) return MDEMOD_ERR_PARAM;
 	if (static_cast<uint64_t>(first) + count > ctx->params.n_streams) return MDEMOD_ERR_RANGE;
 	if (!count) return MDEMOD_OK;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	hipStream_t st = static_cast<hipStream_t>(hip_stream);
 	const DemodStateSoA &s = ctx->st;
@@ -708,15 +679,14 @@ try { MDEMOD_API_ENTER
 		               a.n_streams, b.n_streams);
 		return MDEMOD_ERR_PARAM;
 	}
-	int rc = select_device(dst);
+	int rc = mdm_select_device(dst->params.device);
 	if (rc) return rc;
 	hipStream_t st = static_cast<hipStream_t>(hip_stream);
 	const size_t n = a.n_streams;
 	const DemodStateSoA &d = dst->st, &s = src->st;
-#define CP(field) HIP_TRY(hipMemcpyAsync(d.field, s.field, sizeof(*d.field) * n, hipMemcpyDeviceToDevice, st))
-	CP(agc_gain); CP(agc_bias_re); CP(agc_bias_im); CP(pll_phase); CP(pll_freq); CP(pll_err); CP(t_phase); CP(t_freq); CP(t_prev);
-	CP(inphase); CP(flags); CP(n_samples); CP(n_symbols); CP(first_lock); CP(sym_this_call); CP(ev_this_call); CP(overflow);
-#undef CP
+#define X(field) HIP_TRY(hipMemcpyAsync(d.field, s.field, sizeof(*d.field) * n, hipMemcpyDeviceToDevice, st));
+	MDEMOD_STATE_ARRAYS(X)
+#undef X
 	HIP_TRY(hipMemcpyAsync(d.hist, s.hist, static_cast<size_t>(dst->tab.c.hpad) * n * (dst->tab.use_rw ? 8 : dst->sample_bytes),
 	                       hipMemcpyDeviceToDevice, st));
 	HIP_TRY(hipMemcpyAsync(d.events, s.events, sizeof(mdemod_lock_event) * MDEMOD_MAX_LOCK_EVENTS * n, hipMemcpyDeviceToDevice, st));
@@ -734,7 +704,7 @@ mdemod_compact_soft(mdemod_ctx *ctx, const int8_t *soft_dev, uint64_t soft_strid
                     int8_t *out_dev, uint64_t out_pitch_symbols, void *hip_stream)
 try { MDEMOD_API_ENTER
 	if (!ctx || !soft_dev || !out_dev || (soft_stride_symbols & 7) || (out_pitch_symbols & 7)) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	HIP_TRY(mdemod_launch_compact_rows(soft_dev, soft_stride_symbols, out_dev, out_pitch_symbols, ctx->st.sym_this_call,
 	                                   ctx->params.n_streams, static_cast<hipStream_t>(hip_stream)));
@@ -746,7 +716,7 @@ mdemod_fanin_peer(mdemod_ctx *src, const int8_t *soft_dev, uint64_t soft_stride_
                   int8_t *dst_soft_dev, uint64_t pitch_symbols, uint64_t first_row, uint32_t *dst_counts_dev, void *hip_stream)
 try { MDEMOD_API_ENTER
 	if (!src || !soft_dev || !dst_soft_dev || (soft_stride_symbols & 7) || (pitch_symbols & 7) || dst_device < 0) return MDEMOD_ERR_PARAM;
-	int rc = select_device(src);
+	int rc = mdm_select_device(src->params.device);
 	if (rc) return rc;
 	const int src_device = src->params.device;
 	if (dst_device != src_device) {
@@ -816,7 +786,7 @@ mdemod_get_history(mdemod_ctx *ctx, uint32_t stream, float *iq_pairs, void *hip_
 try { MDEMOD_API_ENTER
 	if (!ctx || !iq_pairs) return MDEMOD_ERR_PARAM;
 	if (stream >= ctx->params.n_streams) return MDEMOD_ERR_RANGE;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	hipStream_t st = static_cast<hipStream_t>(hip_stream);
 	const int hfmt = ctx->tab.use_rw ? 32 : ctx->params.bps;     /* the register-window kernels keep converted floats */
@@ -844,7 +814,7 @@ mdemod_set_history(mdemod_ctx *ctx, uint32_t stream, const float *iq_pairs, void
 try { MDEMOD_API_ENTER
 	if (!ctx || !iq_pairs) return MDEMOD_ERR_PARAM;
 	if (stream >= ctx->params.n_streams) return MDEMOD_ERR_RANGE;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
 	hipStream_t st = static_cast<hipStream_t>(hip_stream);
 	const int hfmt = ctx->tab.use_rw ? 32 : ctx->params.bps;
@@ -907,32 +877,26 @@ int
 mdemod_selftest_sincos(mdemod_ctx *ctx, const float *x, uint32_t n, float *sin_out, float *cos_out)
 try { MDEMOD_API_ENTER
 	if (!ctx || !x || !sin_out || !cos_out) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
+	MdmDevMem mem;
 	float *d = nullptr;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(float) * 3 * static_cast<size_t>(n) + 16));
-	hipError_t e = hipMemcpy(d, x, sizeof(float) * n, hipMemcpyHostToDevice);
-	if (e == hipSuccess) e = mdemod_launch_selftest_sincos(d, n, d + n, d + 2 * static_cast<size_t>(n), nullptr);
-	if (e == hipSuccess) e = hipMemcpy(sin_out, d + n, sizeof(float) * n, hipMemcpyDeviceToHost);
-	if (e == hipSuccess) e = hipMemcpy(cos_out, d + 2 * static_cast<size_t>(n), sizeof(float) * n, hipMemcpyDeviceToHost);
-	(void)hipFree(d);
-	return e == hipSuccess ? MDEMOD_OK : MDEMOD_ERR_HIP;
+	if ((rc = mem.alloc(&d, 3 * static_cast<size_t>(n)))) return rc;
+	HIP_TRY(hipMemcpy(d, x, sizeof(float) * n, hipMemcpyHostToDevice));
+	HIP_TRY(mdemod_launch_selftest_sincos(d, n, d + n, d + 2 * static_cast<size_t>(n), nullptr));
+	HIP_TRY(hipMemcpy(sin_out, d + n, sizeof(float) * n, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(cos_out, d + 2 * static_cast<size_t>(n), sizeof(float) * n, hipMemcpyDeviceToHost));
+	return MDEMOD_OK;
 } MDEMOD_API_CATCH
 
 int
 mdemod_selftest_turncode(mdemod_ctx *ctx, uint64_t *n_checked, uint64_t *n_mismatch)
 try { MDEMOD_API_ENTER
 	if (!ctx || !n_mismatch) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	unsigned long long h[1] = { 0 };
+	const int rc = selftest_count(ctx, h, [](unsigned long long *d) { return mdemod_launch_selftest_turncode(d, nullptr); });
 	if (rc) return rc;
-	unsigned long long *d = nullptr, h = 0;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(h)));
-	hipError_t e = hipMemset(d, 0, sizeof(h));
-	if (e == hipSuccess) e = mdemod_launch_selftest_turncode(d, nullptr);
-	if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost);
-	(void)hipFree(d);
-	if (e != hipSuccess) return MDEMOD_ERR_HIP;
-	*n_mismatch = h;
+	*n_mismatch = h[0];
 	if (n_checked) *n_checked = 2ull * 0x41800000ull;
 	return MDEMOD_OK;
 } MDEMOD_API_CATCH
@@ -941,15 +905,9 @@ int
 mdemod_selftest_cabsf(mdemod_ctx *ctx, uint64_t pairs, uint64_t *n_mismatch, uint64_t *n_fallback)
 try { MDEMOD_API_ENTER
 	if (!ctx || !n_mismatch || !pairs) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	unsigned long long h[2] = { 0, 0 };
+	const int rc = selftest_count(ctx, h, [pairs](unsigned long long *d) { return mdemod_launch_selftest_cabsf(pairs, d, nullptr); });
 	if (rc) return rc;
-	unsigned long long *d = nullptr, h[2] = { 0, 0 };
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(h)));
-	hipError_t e = hipMemset(d, 0, sizeof(h));
-	if (e == hipSuccess) e = mdemod_launch_selftest_cabsf(pairs, d, nullptr);
-	if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-	(void)hipFree(d);
-	if (e != hipSuccess) return MDEMOD_ERR_HIP;
 	*n_mismatch = h[0];
 	if (n_fallback) *n_fallback = h[1];
 	return MDEMOD_OK;
@@ -959,16 +917,10 @@ int
 mdemod_selftest_sinlut(mdemod_ctx *ctx, uint64_t *n_checked, uint64_t *n_mismatch)
 try { MDEMOD_API_ENTER
 	if (!ctx || !n_mismatch) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	unsigned long long h[1] = { 0 };
+	const int rc = selftest_count(ctx, h, [](unsigned long long *d) { return mdemod_launch_selftest_sinlut(d, nullptr); });
 	if (rc) return rc;
-	unsigned long long *d = nullptr, h = 0;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(h)));
-	hipError_t e = hipMemset(d, 0, sizeof(h));
-	if (e == hipSuccess) e = mdemod_launch_selftest_sinlut(d, nullptr);
-	if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost);
-	(void)hipFree(d);
-	if (e != hipSuccess) return MDEMOD_ERR_HIP;
-	*n_mismatch = h;
+	*n_mismatch = h[0];
 	if (n_checked) *n_checked = 4ull * 65536ull;
 	return MDEMOD_OK;
 } MDEMOD_API_CATCH
@@ -977,15 +929,15 @@ int
 mdemod_selftest_hypot(mdemod_ctx *ctx, const float *xy, uint32_t n_pairs, float *out)
 try { MDEMOD_API_ENTER
 	if (!ctx || !xy || !out) return MDEMOD_ERR_PARAM;
-	int rc = select_device(ctx);
+	int rc = mdm_select_device(ctx->params.device);
 	if (rc) return rc;
+	MdmDevMem mem;
 	float *d = nullptr;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(float) * 3 * static_cast<size_t>(n_pairs) + 16));
-	hipError_t e = hipMemcpy(d, xy, sizeof(float) * 2 * n_pairs, hipMemcpyHostToDevice);
-	if (e == hipSuccess) e = mdemod_launch_selftest_hypot(d, n_pairs, d + 2 * static_cast<size_t>(n_pairs), nullptr);
-	if (e == hipSuccess) e = hipMemcpy(out, d + 2 * static_cast<size_t>(n_pairs), sizeof(float) * n_pairs, hipMemcpyDeviceToHost);
-	(void)hipFree(d);
-	return e == hipSuccess ? MDEMOD_OK : MDEMOD_ERR_HIP;
+	if ((rc = mem.alloc(&d, 3 * static_cast<size_t>(n_pairs)))) return rc;
+	HIP_TRY(hipMemcpy(d, xy, sizeof(float) * 2 * n_pairs, hipMemcpyHostToDevice));
+	HIP_TRY(mdemod_launch_selftest_hypot(d, n_pairs, d + 2 * static_cast<size_t>(n_pairs), nullptr));
+	HIP_TRY(hipMemcpy(out, d + 2 * static_cast<size_t>(n_pairs), sizeof(float) * n_pairs, hipMemcpyDeviceToHost));
+	return MDEMOD_OK;
 } MDEMOD_API_CATCH
 
 } /* extern "C" */

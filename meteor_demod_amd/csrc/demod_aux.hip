@@ -9,6 +9,7 @@
 
 #include "demod_internal.h"
 #include "demod_device.h"
+#include "hip_host.h"
 
 #pragma clang fp contract(off)
 
@@ -239,10 +240,7 @@ mdemod_launch_selftest_cabsf(uint64_t pairs, unsigned long long *out_dev, hipStr
 hipError_t
 mdemod_launch_selftest_sinlut(unsigned long long *mismatch_dev, hipStream_t stream)
 {
-	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(selftest_sinlut_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MDEMOD_SIN_LUT_BYTES);
-	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(selftest_sinlut_kernel, dim3(64), dim3(256), MDEMOD_SIN_LUT_BYTES, stream, mismatch_dev);
-	return hipGetLastError();
+	return mdm_launch(selftest_sinlut_kernel, dim3(64), dim3(256), MDEMOD_SIN_LUT_BYTES, stream, mismatch_dev);
 }
 
 /* An empty launch: the first launch of a process loads the library's code objects (tens of milliseconds for the generated

@@ -66,6 +66,11 @@ struct DemodStateSoA {
 	mdemod_lock_event *events;   /* [n_streams][MDEMOD_MAX_LOCK_EVENTS]               */
 };
 
+/* the arrays of one element per stream (all but hist and events), for what treats them alike: allocation, mdemod_copy_state */
+#define MDEMOD_STATE_ARRAYS(X) \
+	X(agc_gain) X(agc_bias_re) X(agc_bias_im) X(pll_phase) X(pll_freq) X(pll_err) X(t_phase) X(t_freq) X(t_prev) X(inphase) \
+	X(flags) X(n_samples) X(n_symbols) X(first_lock) X(sym_this_call) X(ev_this_call) X(overflow)
+
 #define MDEMOD_FLAG_LOCKED       1
 #define MDEMOD_FLAG_LOCKED_ONCE  2
 #define MDEMOD_FLAG_UPDOWN_POS   4

@@ -40,6 +40,7 @@
 
 #include "demod_internal.h"
 #include "demod_device.h"
+#include "hip_host.h"
 
 #pragma clang fp contract(off)
 
@@ -415,11 +416,7 @@ launch_one(const DemodLaunch &L, int block, size_t lds_bytes, hipStream_t stream
 {
 	const uint32_t blocks = (L.n_streams + block - 1) / block;
 	auto kfn = demod_kernel<FMT, OQPSK, NGW, CHUNK, GTAB>;
-	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn),
-	                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(kfn, dim3(blocks), dim3(block), lds_bytes, stream, L);
-	return hipGetLastError();
+	return mdm_launch(kfn, dim3(blocks), dim3(block), lds_bytes, stream, L);
 }
 
 template <int FMT, int OQPSK>

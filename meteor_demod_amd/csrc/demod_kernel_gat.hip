@@ -12,6 +12,7 @@
  * previous block, or within NS samples of the block's end, takes a tap-by-tap path.
  */
 #include "rotwin_body.h"
+#include "hip_host.h"
 
 namespace {
 
@@ -119,10 +120,7 @@ launch_gat(const DemodLaunch &L, size_t lds_bytes, hipStream_t stream)
 {
 	const uint32_t blocks = (L.n_streams + MDEMOD_RW_BLOCK - 1) / MDEMOD_RW_BLOCK;
 	auto kfn = demod_kernel_gat<FMT, OQPSK, KT>;
-	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(kfn, dim3(blocks), dim3(MDEMOD_RW_BLOCK), lds_bytes, stream, L);
-	return hipGetLastError();
+	return mdm_launch(kfn, dim3(blocks), dim3(MDEMOD_RW_BLOCK), lds_bytes, stream, L);
 }
 
 } /* namespace */

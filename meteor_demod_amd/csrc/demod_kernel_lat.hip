@@ -27,6 +27,7 @@
 
 #include "demod_internal.h"
 #include "demod_device.h"
+#include "hip_host.h"
 
 #pragma clang fp contract(off)
 
@@ -273,7 +274,7 @@ demod_kernel_lat(const DemodLaunch L, const float *rrc, int ring_size, int span,
 			flush();
 			continue;
 		}
-#ifdef LAT_EXP_TIMING
+#ifdef LAT_EXP_TIMING   /* (tools/build_exp_lat.sh: see above) */
 		unsigned long long tm_last = __builtin_readcyclecounter();
 		tm_batches++;
 #endif
@@ -396,7 +397,7 @@ demod_kernel_lat(const DemodLaunch L, const float *rrc, int ring_size, int span,
 			const int cidx = steps_done + m - pj;                         /* -1, 0, +1 when the prediction holds */
 			const int idx = kCand * j + cidx + 1;
 			const bool hit = regular && cidx >= -1 && cidx <= 1 && ((ok_mask >> idx) & 1ull);
-#ifdef LAT_EXP_TIMING
+#ifdef LAT_EXP_TIMING   /* (tools/build_exp_lat.sh: see above) */
 			if (hit) tm_c[cidx + 1]++; else tm_miss++;
 #endif
 			if (__builtin_expect(!hit, 0)) { miss = true; break; }                             /* irregular firing: handled after the loop, the batch ends */
@@ -425,7 +426,7 @@ demod_kernel_lat(const DemodLaunch L, const float *rrc, int ring_size, int span,
 		if (miss) careful_firing();
 
 		LAT_TM(tm_serial);
-#ifdef LAT_EXP_TIMING
+#ifdef LAT_EXP_TIMING   /* (tools/build_exp_lat.sh: see above) */
 		tm_fired += (unsigned long long)j;
 #endif
 		/* ---- (3) flush the batch's symbols: lane i writes symbol out_base + i ---- */
@@ -444,7 +445,7 @@ demod_kernel_lat(const DemodLaunch L, const float *rrc, int ring_size, int span,
 		__syncthreads();
 		LAT_TM(tm_commit);
 	}
-#ifdef LAT_EXP_TIMING
+#ifdef LAT_EXP_TIMING   /* (tools/build_exp_lat.sh: see above) */
 	if (lane == 0 && stream == 0 && tm_batches)
 		printf("[lat] %llu batches, %llu firings in them: ticks per batch prefetch %.0f farm %.0f serial %.0f (%.1f per firing) flush %.0f commit %.0f\n", tm_batches, tm_fired,
 		       (double)tm_pf / tm_batches, (double)tm_farm / tm_batches, (double)tm_serial / tm_batches, (double)tm_serial / (double)(tm_fired ? tm_fired : 1),
@@ -501,10 +502,7 @@ launch_lat(const DemodLaunch &L, const float *rrc, int ring_size, int span, int 
 {
 	auto kfn = L.c.oqpsk ? (L.c.step_safe == 6 ? demod_kernel_lat<FMT, 1, 6> : demod_kernel_lat<FMT, 1, 0>)
 	                     : (L.c.step_safe == 14 ? demod_kernel_lat<FMT, 0, 14> : demod_kernel_lat<FMT, 0, 0>);
-	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(kfn, dim3(L.n_streams), dim3(64), lds_bytes, stream, L, rrc, ring_size, span, float_history);
-	return hipGetLastError();
+	return mdm_launch(kfn, dim3(L.n_streams), dim3(64), lds_bytes, stream, L, rrc, ring_size, span, float_history);
 }
 
 } /* namespace */

@@ -11,6 +11,7 @@
  * needs 516 (profiles/r02_kernels.md).
  */
 #include "rotwin_body.h"
+#include "hip_host.h"
 #ifdef ROTPK_ASM_HEADER
 #include ROTPK_ASM_HEADER        /* experimental builds (tools/build_exp_rotp.sh) */
 #else
@@ -173,10 +174,7 @@ hipError_t
 launch_rotp(rotp_kernel_t kfn, int block, const DemodLaunch &L, size_t lds_bytes, hipStream_t stream)
 {
 	const uint32_t blocks = (L.n_streams + block - 1) / block;
-	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(kfn, dim3(blocks), dim3(block), lds_bytes, stream, L);
-	return hipGetLastError();
+	return mdm_launch(kfn, dim3(blocks), dim3(block), lds_bytes, stream, L);
 }
 
 } /* namespace */

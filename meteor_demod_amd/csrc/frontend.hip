@@ -20,11 +20,14 @@
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "demod_internal.h"
 #include "frontend_design.h"
+#include "hip_host.h"
+#include "iq_load.h"
 
 #define FE_BLOCK      256
 #define FE_SPAN_MAX   6144          /* staged samples per tile at most (48 KiB of z) */
@@ -58,21 +61,6 @@ struct FeArgs {
 	uint64_t         bb_stride;
 	uint32_t        *n_out;
 };
-
-template <int FMT>
-__device__ __forceinline__ float2
-fe_load(const void *iq, uint64_t i)
-{
-	if (FMT == 8) {
-		const uchar2 v = static_cast<const uchar2 *>(iq)[i];
-		return make_float2(static_cast<float>(static_cast<int>(v.x) - 128), static_cast<float>(static_cast<int>(v.y) - 128));
-	} else if (FMT == 16) {
-		const short2 v = static_cast<const short2 *>(iq)[i];
-		return make_float2(static_cast<float>(v.x), static_cast<float>(v.y));
-	} else {
-		return static_cast<const float2 *>(iq)[i];
-	}
-}
 
 /* x * e^{j 2 pi p(n) / 2^32}; p rounded to 20 bits */
 __device__ __forceinline__ float2
@@ -129,7 +117,7 @@ fe_filter(FeArgs A)
 			if (static_cast<uint64_t>(idx) < n_abs) {
 				v = hist[c.H - static_cast<int64_t>(n_abs - static_cast<uint64_t>(idx))];
 			} else if (static_cast<uint64_t>(idx) < n_abs + n) {
-				v = fe_load<FMT>(A.iq, in_off + (static_cast<uint64_t>(idx) - n_abs));
+				v = md_load_iq<FMT>(A.iq, in_off + (static_cast<uint64_t>(idx) - n_abs));
 				if (mix) v = fe_mix(v, static_cast<uint64_t>(idx), step, trig);
 			}
 		}
@@ -218,7 +206,7 @@ fe_advance(FeArgs A)
 			if (static_cast<uint64_t>(idx) < n_abs) {
 				v = hin[c.H - static_cast<int64_t>(n_abs - static_cast<uint64_t>(idx))];
 			} else {
-				v = fe_load<FMT>(A.iq, in_off + (static_cast<uint64_t>(idx) - n_abs));
+				v = md_load_iq<FMT>(A.iq, in_off + (static_cast<uint64_t>(idx) - n_abs));
 				if (mix) v = fe_mix(v, static_cast<uint64_t>(idx), step, trig);
 			}
 		}
@@ -261,38 +249,10 @@ struct mdemod_fe {
 	size_t         in_bytes;
 	uint64_t      *d_in_off;
 	uint32_t      *d_in_cnt;
-	std::vector<void *> allocs;
+	MdmDevMem      mem;
 };
 
 namespace {
-
-#define FE_TRY(expr)                                                                                 \
-	do {                                                                                             \
-		hipError_t e_ = (expr);                                                                      \
-		if (e_ != hipSuccess) {                                                                      \
-			mdm_note_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-			(void)hipGetLastError();                                                                 \
-			return e_ == hipErrorOutOfMemory ? MDEMOD_ERR_NOMEM : MDEMOD_ERR_HIP;                    \
-		}                                                                                            \
-	} while (0)
-
-template <typename T>
-int
-fe_alloc(mdemod_fe *fe, T **ptr, size_t count)
-{
-	void *p = nullptr;
-	FE_TRY(hipMalloc(&p, count * sizeof(T) + 16));
-	fe->allocs.push_back(p);
-	*ptr = static_cast<T *>(p);
-	return MDEMOD_OK;
-}
-
-void
-fe_free(mdemod_fe *fe, void *p)
-{
-	for (auto &a : fe->allocs)
-		if (a == p) { (void)hipFree(a); a = nullptr; }
-}
 
 /* tile geometry: 256 outputs per block (512 / 1024 when they fit), else G threads per output; the span always fits FE_SPAN_MAX */
 void
@@ -321,20 +281,27 @@ fe_plan(const FeDesign &d, bool mix, FeConsts &c, size_t &lds)
 }
 
 int
-fe_select(const mdemod_fe *fe)
-{
-	(void)hipGetLastError();
-	FE_TRY(hipSetDevice(fe->input.device));
-	return MDEMOD_OK;
-}
-
-int
 fe_reset_state(mdemod_fe *fe, hipStream_t st)
 {
 	const size_t n = fe->input.n_streams;
-	FE_TRY(hipMemsetAsync(fe->d_n_abs, 0, n * sizeof(uint64_t), st));
-	FE_TRY(hipMemsetAsync(fe->d_hist[0], 0, n * (fe->c.H ? fe->c.H : 1) * sizeof(float2), st));
+	HIP_TRY(hipMemsetAsync(fe->d_n_abs, 0, n * sizeof(uint64_t), st));
+	HIP_TRY(hipMemsetAsync(fe->d_hist[0], 0, n * (fe->c.H ? fe->c.H : 1) * sizeof(float2), st));
 	fe->parity = 0;
+	return MDEMOD_OK;
+}
+
+/* fe_create: the tables and the zero state, on a private stream that is waited for */
+int
+fe_upload(mdemod_fe *fe, const std::vector<float> &taps, const std::vector<float2> &trig)
+{
+	MdmStream own;
+	HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+	HIP_TRY(hipMemcpyAsync(fe->d_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, own.s));
+	HIP_TRY(hipMemcpyAsync(fe->d_trig, trig.data(), trig.size() * sizeof(float2), hipMemcpyHostToDevice, own.s));
+	HIP_TRY(hipMemcpyAsync(fe->d_steps, fe->design.steps.data(), fe->design.steps.size() * sizeof(uint32_t), hipMemcpyHostToDevice, own.s));
+	const int rc = fe_reset_state(fe, own.s);
+	if (rc) return rc;
+	HIP_TRY(hipStreamSynchronize(own.s));
 	return MDEMOD_OK;
 }
 
@@ -360,22 +327,18 @@ fe_create(const mdemod_params *input, const mdemod_fe_params *p, bool with_inner
 		ip.bps = 32;
 		FE_CREATE_TRY(mdemod_create(&ip, &fe->inner));             /* (its refusals pass through with their own text) */
 	}
-	{
-		(void)hipGetLastError();
-		hipError_t e = hipSetDevice(input->device);
-		if (e != hipSuccess) { mdm_note_error("no usable HIP device %d: %s", input->device, hipGetErrorString(e)); (void)hipGetLastError(); mdemod_fe_destroy(fe); return MDEMOD_ERR_HIP; }
-	}
+	FE_CREATE_TRY(mdm_select_device(input->device));
 	const size_t n = input->n_streams, H = fe->c.H ? fe->c.H : 1;
-	FE_CREATE_TRY(fe_alloc(fe, &fe->d_taps, static_cast<size_t>(fe->c.D) * fe->c.nq0));
-	FE_CREATE_TRY(fe_alloc(fe, &fe->d_trig, 2 * FE_TRIG));
-	FE_CREATE_TRY(fe_alloc(fe, &fe->d_steps, n));
-	FE_CREATE_TRY(fe_alloc(fe, &fe->d_n_abs, n));
-	FE_CREATE_TRY(fe_alloc(fe, &fe->d_hist[0], n * H));
-	FE_CREATE_TRY(fe_alloc(fe, &fe->d_hist[1], n * H));
-	FE_CREATE_TRY(fe_alloc(fe, &fe->d_bb_off, n));
-	FE_CREATE_TRY(fe_alloc(fe, &fe->d_bb_cnt, n));
-	FE_CREATE_TRY(fe_alloc(fe, &fe->d_in_off, n));
-	FE_CREATE_TRY(fe_alloc(fe, &fe->d_in_cnt, n));
+	FE_CREATE_TRY(fe->mem.alloc(&fe->d_taps, static_cast<size_t>(fe->c.D) * fe->c.nq0));
+	FE_CREATE_TRY(fe->mem.alloc(&fe->d_trig, 2 * FE_TRIG));
+	FE_CREATE_TRY(fe->mem.alloc(&fe->d_steps, n));
+	FE_CREATE_TRY(fe->mem.alloc(&fe->d_n_abs, n));
+	FE_CREATE_TRY(fe->mem.alloc(&fe->d_hist[0], n * H));
+	FE_CREATE_TRY(fe->mem.alloc(&fe->d_hist[1], n * H));
+	FE_CREATE_TRY(fe->mem.alloc(&fe->d_bb_off, n));
+	FE_CREATE_TRY(fe->mem.alloc(&fe->d_bb_cnt, n));
+	FE_CREATE_TRY(fe->mem.alloc(&fe->d_in_off, n));
+	FE_CREATE_TRY(fe->mem.alloc(&fe->d_in_cnt, n));
 	/* phase-major taps, zero where a phase has one tap fewer; the mixer's tables in double, rounded once */
 	std::vector<float> ht(static_cast<size_t>(fe->c.D) * fe->c.nq0, 0.0f);
 	for (int r = 0; r < fe->c.D; r++)
@@ -387,20 +350,7 @@ fe_create(const mdemod_params *input, const mdemod_fe_params *p, bool with_inner
 		trig[i] = make_float2(static_cast<float>(cos(a)), static_cast<float>(sin(a)));
 		trig[FE_TRIG + i] = make_float2(static_cast<float>(cos(b)), static_cast<float>(sin(b)));
 	}
-	hipStream_t s0 = nullptr;
-	hipError_t e = hipStreamCreateWithFlags(&s0, hipStreamNonBlocking);
-	if (e == hipSuccess) e = hipMemcpyAsync(fe->d_taps, ht.data(), ht.size() * sizeof(float), hipMemcpyHostToDevice, s0);
-	if (e == hipSuccess) e = hipMemcpyAsync(fe->d_trig, trig.data(), trig.size() * sizeof(float2), hipMemcpyHostToDevice, s0);
-	if (e == hipSuccess) e = hipMemcpyAsync(fe->d_steps, d.steps.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s0);
-	int rc_reset = e == hipSuccess ? fe_reset_state(fe, s0) : MDEMOD_OK;
-	if (e == hipSuccess) e = hipStreamSynchronize(s0);
-	if (s0) (void)hipStreamDestroy(s0);
-	if (e != hipSuccess || rc_reset) {
-		if (e != hipSuccess) mdm_note_error("mdemod_fe_create: uploading the tables failed: %s", hipGetErrorString(e));
-		(void)hipGetLastError();
-		mdemod_fe_destroy(fe);
-		return rc_reset ? rc_reset : MDEMOD_ERR_HIP;
-	}
+	FE_CREATE_TRY(fe_upload(fe, ht, trig));
 #undef FE_CREATE_TRY
 	*out = fe;
 	return MDEMOD_OK;
@@ -427,14 +377,12 @@ fe_launch(mdemod_fe *fe, const void *iq, const uint64_t *off, const uint32_t *cn
 #define FE_PICK(F) (fe->c.R == 4 ? fe_filter<F, 4> : (fe->c.R == 2 ? fe_filter<F, 2> : fe_filter<F, 1>))
 		kfn = fmt == 8 ? FE_PICK(8) : (fmt == 16 ? FE_PICK(16) : FE_PICK(32));
 #undef FE_PICK
-		FE_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(fe->lds_bytes)));
-		hipLaunchKernelGGL(kfn, dim3(static_cast<uint32_t>(blocks)), dim3(FE_BLOCK), fe->lds_bytes, st, A);
-		FE_TRY(hipGetLastError());
+		HIP_TRY(mdm_launch(kfn, dim3(static_cast<uint32_t>(blocks)), dim3(FE_BLOCK), fe->lds_bytes, st, A));
 	}
 	if (fmt == 8) hipLaunchKernelGGL(fe_advance<8>, dim3(fe->c.n_streams), dim3(FE_BLOCK), 0, st, A);
 	else if (fmt == 16) hipLaunchKernelGGL(fe_advance<16>, dim3(fe->c.n_streams), dim3(FE_BLOCK), 0, st, A);
 	else hipLaunchKernelGGL(fe_advance<32>, dim3(fe->c.n_streams), dim3(FE_BLOCK), 0, st, A);
-	FE_TRY(hipGetLastError());
+	HIP_TRY(hipGetLastError());
 	fe->parity ^= 1;
 	return MDEMOD_OK;
 }
@@ -446,15 +394,15 @@ fe_grow_bb(mdemod_fe *fe, uint64_t outputs, hipStream_t st)
 	const uint64_t want = (outputs + 63) / 64 * 64;
 	if (fe->d_bb && fe->bb_stride >= want) return MDEMOD_OK;
 	if (fe->d_bb) {
-		FE_TRY(hipStreamSynchronize(st));                           /* (a call still queued may read the old rows) */
-		fe_free(fe, fe->d_bb);
+		HIP_TRY(hipStreamSynchronize(st));                           /* (a call still queued may read the old rows) */
+		fe->mem.release(fe->d_bb);
 		fe->d_bb = nullptr;
 	}
-	int rc = fe_alloc(fe, &fe->d_bb, want * fe->c.n_streams);
+	int rc = fe->mem.alloc(&fe->d_bb, want * fe->c.n_streams);
 	if (rc) return rc;
 	fe->bb_stride = want;
 	hipLaunchKernelGGL(fe_fill_rows, dim3((fe->c.n_streams + 255) / 256), dim3(256), 0, st, fe->d_bb_off, want, fe->c.n_streams);
-	FE_TRY(hipGetLastError());
+	HIP_TRY(hipGetLastError());
 	return MDEMOD_OK;
 }
 
@@ -473,16 +421,15 @@ mdemod_fe_destroy(mdemod_fe *fe)
 {
 	if (!fe) return;
 	(void)hipSetDevice(fe->input.device);
-	for (void *p : fe->allocs) if (p) (void)hipFree(p);
 	if (fe->inner) mdemod_destroy(fe->inner);
-	delete fe;
+	delete fe;                                                      /* (with everything fe->mem holds) */
 }
 
 int
 mdemod_fe_reset(mdemod_fe *fe, void *hip_stream)
 try { MDEMOD_API_ENTER
 	if (!fe) return MDEMOD_ERR_PARAM;
-	int rc = fe_select(fe);
+	int rc = mdm_select_device(fe->input.device);
 	if (rc) return rc;
 	rc = fe_reset_state(fe, static_cast<hipStream_t>(hip_stream));
 	if (rc) return rc;
@@ -508,7 +455,7 @@ mdemod_fe_baseband_device(mdemod_fe *fe, const void *iq_dev, const uint64_t *iq_
 try { MDEMOD_API_ENTER
 	if (!fe || !iq_dev || !iq_offset_dev || !n_samples_dev || !bb_dev || !n_out_dev) { mdm_note_error("mdemod_fe_baseband_device: a pointer is NULL"); return MDEMOD_ERR_PARAM; }
 	if (bb_cap > bb_stride) { mdm_note_error("mdemod_fe_baseband_device: bb_cap %u exceeds the row pitch %llu", bb_cap, static_cast<unsigned long long>(bb_stride)); return MDEMOD_ERR_PARAM; }
-	int rc = fe_select(fe);
+	int rc = mdm_select_device(fe->input.device);
 	if (rc) return rc;
 	return fe_launch(fe, iq_dev, iq_offset_dev, n_samples_dev, reinterpret_cast<float2 *>(bb_dev), bb_stride, bb_cap, n_out_dev,
 	                 static_cast<hipStream_t>(hip_stream));
@@ -521,7 +468,7 @@ mdemod_fe_process_device(mdemod_fe *fe, const void *iq_dev, const uint64_t *iq_o
 try { MDEMOD_API_ENTER
 	if (!fe || !fe->inner || !iq_dev || !iq_offset_dev || !n_samples_dev || !soft_dev) { mdm_note_error("mdemod_fe_process_device: a pointer is NULL"); return MDEMOD_ERR_PARAM; }
 	if (soft_cap_symbols > soft_stride_symbols) { mdm_note_error("mdemod_fe_process_device: soft capacity beyond the row pitch"); return MDEMOD_ERR_PARAM; }
-	int rc = fe_select(fe);
+	int rc = mdm_select_device(fe->input.device);
 	if (rc) return rc;
 	hipStream_t st = static_cast<hipStream_t>(hip_stream);
 	const uint64_t outs = mdemod_fe_max_outputs(fe, max_samples);
@@ -537,7 +484,7 @@ mdemod_fe_process_host(mdemod_fe *fe, const void *const *iq_host, const uint32_t
                        int8_t *const *soft_host, const uint32_t *soft_cap, uint32_t *n_symbols)
 try { MDEMOD_API_ENTER
 	if (!fe || !fe->inner || !iq_host || !n_samples || !soft_host || !soft_cap || !n_symbols) { mdm_note_error("mdemod_fe_process_host: a pointer is NULL"); return MDEMOD_ERR_PARAM; }
-	int rc = fe_select(fe);
+	int rc = mdm_select_device(fe->input.device);
 	if (rc) return rc;
 	/* plain and synchronous: the blocks side by side in one device buffer, the front end, the baseband back to the host, and the
 	   inner context's own host path on it (8 / D bytes per input sample come back: a fraction of what went in for D >= 2) */
@@ -553,31 +500,31 @@ try { MDEMOD_API_ENTER
 		if (n_samples[s] > most) most = n_samples[s];
 	}
 	hipStream_t st = nullptr;
-	FE_TRY(hipDeviceSynchronize());
+	HIP_TRY(hipDeviceSynchronize());
 	if (total * sb > fe->in_bytes) {
-		if (fe->d_in) { fe_free(fe, fe->d_in); fe->d_in = nullptr; fe->in_bytes = 0; }
+		if (fe->d_in) { fe->mem.release(fe->d_in); fe->d_in = nullptr; fe->in_bytes = 0; }
 		unsigned char *p = nullptr;
-		rc = fe_alloc(fe, &p, total * sb);
+		rc = fe->mem.alloc(&p, total * sb);
 		if (rc) return rc;
 		fe->d_in = p;
 		fe->in_bytes = total * sb;
 	}
 	for (uint32_t s = 0; s < ns; s++)
-		if (n_samples[s]) FE_TRY(hipMemcpy(static_cast<unsigned char *>(fe->d_in) + off[s] * sb, iq_host[s], n_samples[s] * sb, hipMemcpyHostToDevice));
-	FE_TRY(hipMemcpy(fe->d_in_off, off.data(), ns * sizeof(uint64_t), hipMemcpyHostToDevice));
-	FE_TRY(hipMemcpy(fe->d_in_cnt, n_samples, ns * sizeof(uint32_t), hipMemcpyHostToDevice));
+		if (n_samples[s]) HIP_TRY(hipMemcpy(static_cast<unsigned char *>(fe->d_in) + off[s] * sb, iq_host[s], n_samples[s] * sb, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(fe->d_in_off, off.data(), ns * sizeof(uint64_t), hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(fe->d_in_cnt, n_samples, ns * sizeof(uint32_t), hipMemcpyHostToDevice));
 	const uint64_t outs = mdemod_fe_max_outputs(fe, most);
 	rc = fe_grow_bb(fe, outs, st);
 	if (rc) return rc;
 	rc = fe_launch(fe, fe->d_in ? fe->d_in : fe->d_bb, fe->d_in_off, fe->d_in_cnt, fe->d_bb, fe->bb_stride, static_cast<uint32_t>(outs), fe->d_bb_cnt, st);
 	if (rc) return rc;
 	std::vector<uint32_t> cnt(ns);
-	FE_TRY(hipMemcpy(cnt.data(), fe->d_bb_cnt, ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(cnt.data(), fe->d_bb_cnt, ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	std::vector<float> bb(static_cast<size_t>(fe->bb_stride) * 2 * ns);
 	std::vector<const void *> rows(ns);
 	for (uint32_t s = 0; s < ns; s++) {
 		float *row = bb.data() + static_cast<size_t>(s) * fe->bb_stride * 2;
-		if (cnt[s]) FE_TRY(hipMemcpy(row, fe->d_bb + static_cast<size_t>(s) * fe->bb_stride, cnt[s] * sizeof(float2), hipMemcpyDeviceToHost));
+		if (cnt[s]) HIP_TRY(hipMemcpy(row, fe->d_bb + static_cast<size_t>(s) * fe->bb_stride, cnt[s] * sizeof(float2), hipMemcpyDeviceToHost));
 		rows[s] = row;
 	}
 	return mdemod_process_host(fe->inner, rows.data(), cnt.data(), soft_host, soft_cap, n_symbols);
@@ -596,36 +543,39 @@ try { MDEMOD_API_ENTER
 	mdemod_fe *fe = nullptr;
 	int rc = fe_create(&one, &fp, false, &fe);
 	if (rc) return rc;
-	struct Guard { mdemod_fe *f; void *a, *b, *c; ~Guard() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); mdemod_fe_destroy(f); } } g{fe, nullptr, nullptr, nullptr};
+	/* (the buffers below live in the front end's own list: they go with it, on every way out) */
+	const std::unique_ptr<mdemod_fe, decltype(&mdemod_fe_destroy)> owner(fe, mdemod_fe_destroy);
 	const size_t sb = 2 * static_cast<size_t>(input->bps) / 8;
 	const uint64_t n_bb = mdemod_fe_max_outputs(fe, n_samples);
 	/* the input in pieces of 2^26 samples (one device buffer, reused), the baseband of the whole recording in one */
 	const uint64_t piece = n_samples < (1ull << 26) ? (n_samples ? n_samples : 1) : (1ull << 26);
-	FE_TRY(hipMalloc(&g.a, piece * sb + 16));
-	FE_TRY(hipMalloc(&g.b, n_bb * sizeof(float2) + 64));
-	FE_TRY(hipMalloc(&g.c, soft_cap_symbols * 2 + 16));
+	unsigned char *d_in = nullptr;
+	float2 *d_bb = nullptr;
+	int8_t *d_soft = nullptr;
+	if ((rc = fe->mem.alloc(&d_in, piece * sb)) || (rc = fe->mem.alloc(&d_bb, n_bb)) || (rc = fe->mem.alloc(&d_soft, soft_cap_symbols * 2)))
+		return rc;
 	hipStream_t st = nullptr;
 	uint64_t done = 0, produced = 0;
 	while (done < n_samples) {
 		const uint32_t n = static_cast<uint32_t>(n_samples - done < piece ? n_samples - done : piece);
-		FE_TRY(hipMemcpy(g.a, static_cast<const unsigned char *>(iq_host) + done * sb, n * sb, hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(d_in, static_cast<const unsigned char *>(iq_host) + done * sb, n * sb, hipMemcpyHostToDevice));
 		const uint64_t zero = 0;
-		FE_TRY(hipMemcpy(fe->d_in_off, &zero, sizeof(zero), hipMemcpyHostToDevice));
-		FE_TRY(hipMemcpy(fe->d_in_cnt, &n, sizeof(n), hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(fe->d_in_off, &zero, sizeof(zero), hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(fe->d_in_cnt, &n, sizeof(n), hipMemcpyHostToDevice));
 		const uint64_t outs = mdemod_fe_max_outputs(fe, n);
-		rc = fe_launch(fe, g.a, fe->d_in_off, fe->d_in_cnt, static_cast<float2 *>(g.b) + produced, outs, static_cast<uint32_t>(outs), fe->d_bb_cnt, st);
+		rc = fe_launch(fe, d_in, fe->d_in_off, fe->d_in_cnt, d_bb + produced, outs, static_cast<uint32_t>(outs), fe->d_bb_cnt, st);
 		if (rc) return rc;
 		uint32_t got = 0;
-		FE_TRY(hipMemcpy(&got, fe->d_bb_cnt, sizeof(got), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(&got, fe->d_bb_cnt, sizeof(got), hipMemcpyDeviceToHost));
 		produced += got;
 		done += n;
 	}
 	mdemod_params ip = one;
 	ip.samplerate = fe->design.samplerate_out;
 	ip.bps = 32;
-	rc = mdemod_demodulate_recording(&ip, opts, g.b, produced, static_cast<int8_t *>(g.c), soft_cap_symbols, report, nullptr);
+	rc = mdemod_demodulate_recording(&ip, opts, d_bb, produced, d_soft, soft_cap_symbols, report, nullptr);
 	if (rc) return rc;
-	FE_TRY(hipMemcpy(soft_host, g.c, report->n_symbols * 2, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(soft_host, d_soft, report->n_symbols * 2, hipMemcpyDeviceToHost));
 	return MDEMOD_OK;
 } MDEMOD_API_CATCH
 

@@ -41,20 +41,10 @@
 #include <unistd.h>
 
 #include "demod_internal.h"
+#include "hip_host.h"
 #include "pack_pool.h"
 
 namespace {
-
-#define PIPE_TRY(expr)                                                                          \
-	do {                                                                                        \
-		hipError_t e_ = (expr);                                                                 \
-		if (e_ != hipSuccess) {                                                                 \
-			mdm_note_error("%s failed: %s (%s:%d)", #expr,                                   \
-			        hipGetErrorString(e_), __FILE__, __LINE__);                                 \
-			(void)hipGetLastError();                                                            \
-			return e_ == hipErrorOutOfMemory ? MDEMOD_ERR_NOMEM : MDEMOD_ERR_HIP;               \
-		}                                                                                       \
-	} while (0)
 
 constexpr int kSlots = 3;        /* staging sets: one being filled / copied in, one under the kernel / copied out, one being handed back */
 
@@ -110,7 +100,7 @@ grow_host_any(T **host, size_t *have, size_t need)
 	if (*host) (void)hipHostFree(*host);
 	*host = nullptr; *have = 0;
 	need += need / 8;                                        /* a little headroom: fewer re-allocations */
-	PIPE_TRY(hipHostMalloc(reinterpret_cast<void **>(host), need, hipHostMallocDefault));
+	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(host), need, hipHostMallocDefault));
 	*have = need;
 	return MDEMOD_OK;
 }
@@ -122,7 +112,7 @@ grow_host(int8_t **host, size_t *have, size_t need)
 	if (*host) (void)hipHostFree(*host);
 	*host = nullptr; *have = 0;
 	need += need / 8;
-	PIPE_TRY(hipHostMalloc(reinterpret_cast<void **>(host), need, hipHostMallocDefault));
+	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(host), need, hipHostMallocDefault));
 	*have = need;
 	return MDEMOD_OK;
 }
@@ -135,7 +125,7 @@ grow_dev(T **dev, size_t *have, size_t need)
 	if (*dev) (void)hipFree(*dev);
 	*dev = nullptr; *have = 0;
 	need += need / 8;
-	PIPE_TRY(hipMalloc(reinterpret_cast<void **>(dev), need));
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(dev), need));
 	*have = need;
 	return MDEMOD_OK;
 }
@@ -150,25 +140,25 @@ pipe_init(HostPipe *p, uint32_t ns)
 	{
 		int lo = 0, hi = 0;
 		(void)hipDeviceGetStreamPriorityRange(&lo, &hi);          /* lo: numerically greatest = least urgent */
-		if (!p->s_in) PIPE_TRY(hipStreamCreateWithPriority(&p->s_in, hipStreamNonBlocking, lo));
-		if (!p->s_cmp) PIPE_TRY(hipStreamCreateWithPriority(&p->s_cmp, hipStreamNonBlocking, hi));
-		if (!p->s_out) PIPE_TRY(hipStreamCreateWithPriority(&p->s_out, hipStreamNonBlocking, hi));
+		if (!p->s_in) HIP_TRY(hipStreamCreateWithPriority(&p->s_in, hipStreamNonBlocking, lo));
+		if (!p->s_cmp) HIP_TRY(hipStreamCreateWithPriority(&p->s_cmp, hipStreamNonBlocking, hi));
+		if (!p->s_out) HIP_TRY(hipStreamCreateWithPriority(&p->s_out, hipStreamNonBlocking, hi));
 	}
 #endif
-	if (!p->s_in) PIPE_TRY(hipStreamCreateWithFlags(&p->s_in, hipStreamNonBlocking));
-	if (!p->s_cmp) PIPE_TRY(hipStreamCreateWithFlags(&p->s_cmp, hipStreamNonBlocking));
-	if (!p->s_out) PIPE_TRY(hipStreamCreateWithFlags(&p->s_out, hipStreamNonBlocking));
+	if (!p->s_in) HIP_TRY(hipStreamCreateWithFlags(&p->s_in, hipStreamNonBlocking));
+	if (!p->s_cmp) HIP_TRY(hipStreamCreateWithFlags(&p->s_cmp, hipStreamNonBlocking));
+	if (!p->s_out) HIP_TRY(hipStreamCreateWithFlags(&p->s_out, hipStreamNonBlocking));
 	for (Slot &s : p->slot) {
-		if (!s.ev_in) PIPE_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
-		if (!s.ev_k) PIPE_TRY(hipEventCreateWithFlags(&s.ev_k, hipEventDisableTiming));
-		if (!s.ev_out) PIPE_TRY(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
-		if (!s.h_off) PIPE_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_off), sizeof(uint64_t) * ns, hipHostMallocDefault));
-		if (!s.h_cnt) PIPE_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_cnt), sizeof(uint32_t) * ns, hipHostMallocDefault));
-		if (!s.h_prod) PIPE_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_prod), sizeof(uint32_t) * ns, hipHostMallocDefault));
-		if (!s.h_ev) PIPE_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_ev), sizeof(uint32_t) * ns, hipHostMallocDefault));
-		if (!s.d_off) PIPE_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_off), sizeof(uint64_t) * ns));
-		if (!s.d_cnt) PIPE_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_cnt), sizeof(uint32_t) * ns));
-		if (!s.d_events) PIPE_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_events), sizeof(mdemod_lock_event) * MDEMOD_MAX_LOCK_EVENTS * ns));
+		if (!s.ev_in) HIP_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
+		if (!s.ev_k) HIP_TRY(hipEventCreateWithFlags(&s.ev_k, hipEventDisableTiming));
+		if (!s.ev_out) HIP_TRY(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
+		if (!s.h_off) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_off), sizeof(uint64_t) * ns, hipHostMallocDefault));
+		if (!s.h_cnt) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_cnt), sizeof(uint32_t) * ns, hipHostMallocDefault));
+		if (!s.h_prod) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_prod), sizeof(uint32_t) * ns, hipHostMallocDefault));
+		if (!s.h_ev) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_ev), sizeof(uint32_t) * ns, hipHostMallocDefault));
+		if (!s.d_off) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_off), sizeof(uint64_t) * ns));
+		if (!s.d_cnt) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_cnt), sizeof(uint32_t) * ns));
+		if (!s.d_events) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_events), sizeof(mdemod_lock_event) * MDEMOD_MAX_LOCK_EVENTS * ns));
 	}
 	p->ready = true;
 	return MDEMOD_OK;
@@ -263,7 +253,7 @@ mdemod_hostpipe_pin(void **pipe_slot, const void *base, size_t bytes)
 		mdm_note_error("mdemod_pin_host_buffer: a part of [%p, +%zu) is registered already, the range as a whole is not", base, bytes);
 		return MDEMOD_ERR_PARAM;
 	}
-	PIPE_TRY(e);
+	HIP_TRY(e);
 	p->pins.push_back({ b, bytes, true });
 	return MDEMOD_OK;
 }
@@ -276,7 +266,7 @@ mdemod_hostpipe_unpin(void *opaque, const void *base)
 	for (size_t i = 0; i < p->pins.size(); i++)
 		if (p->pins[i].base == base) {
 			/* (nothing of this context is in flight: mdemod_process_host is synchronous) */
-			if (p->pins[i].ours) PIPE_TRY(hipHostUnregister(const_cast<unsigned char *>(p->pins[i].base)));
+			if (p->pins[i].ours) HIP_TRY(hipHostUnregister(const_cast<unsigned char *>(p->pins[i].base)));
 			p->pins.erase(p->pins.begin() + static_cast<long>(i));
 			return MDEMOD_OK;
 		}
@@ -379,7 +369,7 @@ mdemod_hostpipe_run(mdemod_ctx *ctx, void **pipe_slot, const DemodStateSoA &st, 
 	auto sub_lo = [&](uint32_t s, uint32_t k) { return static_cast<uint32_t>(static_cast<uint64_t>(n_samples[s]) * cumw[k] / cumw[K]); };
 
 	auto unpack = [&](Slot &sl) -> int {
-		TR(tr_wait_out, PIPE_TRY(hipEventSynchronize(sl.ev_out)));
+		TR(tr_wait_out, HIP_TRY(hipEventSynchronize(sl.ev_out)));
 		/* common case: every row fits the nominal pitch and h_soft holds it.  A stream that fired on (almost) every sample
 		 * (full-scale transient) exceeds it: then the rows are fetched again, 2-D, from the hard-pitch buffer. */
 		uint32_t widest = 0;
@@ -391,9 +381,9 @@ mdemod_hostpipe_run(mdemod_ctx *ctx, void **pipe_slot, const DemodStateSoA &st, 
 		if (widest > sl.pitch) {
 			int rcg = grow_host(&sl.h_soft, &sl.h_soft_bytes, static_cast<size_t>(widest) * 2 * ns + 16);
 			if (rcg) return rcg;
-			PIPE_TRY(hipMemcpy2DAsync(sl.h_soft, static_cast<size_t>(widest) * 2, sl.d_soft, static_cast<size_t>(sl.cap) * 2,
+			HIP_TRY(hipMemcpy2DAsync(sl.h_soft, static_cast<size_t>(widest) * 2, sl.d_soft, static_cast<size_t>(sl.cap) * 2,
 			                          static_cast<size_t>(widest) * 2, ns, hipMemcpyDeviceToHost, p->s_out));
-			PIPE_TRY(hipStreamSynchronize(p->s_out));
+			HIP_TRY(hipStreamSynchronize(p->s_out));
 			sl.width = widest;
 		}
 		std::vector<uint64_t> w(ns);
@@ -428,7 +418,7 @@ mdemod_hostpipe_run(mdemod_ctx *ctx, void **pipe_slot, const DemodStateSoA &st, 
 				const uint32_t take = std::min<uint32_t>(n_new, MDEMOD_MAX_LOCK_EVENTS - have);
 				if (take) {
 					/* from the slot's own copy (taken on the compute stream right after its kernel; ev_out follows it) */
-					PIPE_TRY(hipMemcpy(&ev_store[static_cast<size_t>(s) * MDEMOD_MAX_LOCK_EVENTS + have],
+					HIP_TRY(hipMemcpy(&ev_store[static_cast<size_t>(s) * MDEMOD_MAX_LOCK_EVENTS + have],
 					                   sl.d_events + static_cast<size_t>(s) * MDEMOD_MAX_LOCK_EVENTS, sizeof(mdemod_lock_event) * take, hipMemcpyDeviceToHost));
 				}
 			}
@@ -442,7 +432,7 @@ mdemod_hostpipe_run(mdemod_ctx *ctx, void **pipe_slot, const DemodStateSoA &st, 
 		/* ---- layout of sub-block k ---- */
 		std::vector<uint64_t> wpre(ns);
 		uint64_t pos = 0; uint32_t sub_max = 0;
-		TR(tr_wait_in, if (sl.used_in) PIPE_TRY(hipEventSynchronize(sl.ev_in)));          /* h_iq / h_off / h_cnt of this slot are free again */
+		TR(tr_wait_in, if (sl.used_in) HIP_TRY(hipEventSynchronize(sl.ev_in)));          /* h_iq / h_off / h_cnt of this slot are free again */
 		for (uint32_t s = 0; s < ns; s++) {
 			const uint32_t lo = sub_lo(s, k), hi = sub_lo(s, k + 1);
 			sl.h_off[s] = pos; sl.h_cnt[s] = hi - lo;
@@ -466,7 +456,7 @@ mdemod_hostpipe_run(mdemod_ctx *ctx, void **pipe_slot, const DemodStateSoA &st, 
 		const size_t soft_bytes = static_cast<size_t>(cap) * 2 * ns, pack_bytes = static_cast<size_t>(pitch) * 2 * ns;
 		if (iq_bytes > sl.d_iq_bytes || (!direct_k && iq_bytes > sl.h_iq_bytes) || soft_bytes > sl.d_soft_bytes || pack_bytes > sl.d_pack_bytes || pack_bytes > sl.h_soft_bytes) {
 			/* the slot's previous sub-block must be completely through before its buffers are replaced */
-			if (sl.used_out) PIPE_TRY(hipEventSynchronize(sl.ev_out));
+			if (sl.used_out) HIP_TRY(hipEventSynchronize(sl.ev_out));
 			rc = grow_dev(&sl.d_iq, &sl.d_iq_bytes, iq_bytes);
 			if (rc) return rc;
 			if (!direct_k) { rc = grow_host_any(&sl.h_iq, &sl.h_iq_bytes, iq_bytes); if (rc) return rc; }
@@ -488,7 +478,7 @@ mdemod_hostpipe_run(mdemod_ctx *ctx, void **pipe_slot, const DemodStateSoA &st, 
 			_mm_sfence();                                                  /* the non-temporal stores of this thread are out before the copy engine reads the ring */
 		}));
 		/* ---- H2D: after the kernel that last read this slot's device input ---- */
-		if (sl.used_k) PIPE_TRY(hipStreamWaitEvent(p->s_in, sl.ev_k, 0));
+		if (sl.used_k) HIP_TRY(hipStreamWaitEvent(p->s_in, sl.ev_k, 0));
 		/* Never more than two copy-ins queued: a 2-D copy that is enqueued while two are still ahead of it runs at 38 GB/s instead of
 		 * 56, and so does the one behind it (r05 timeline: the first three of a pinned batch, which the host enqueues within 0.2 ms
 		 * of each other; any later one that finds two ahead of it).  Waiting for the copy before the previous one costs nothing:
@@ -496,7 +486,7 @@ mdemod_hostpipe_run(mdemod_ctx *ctx, void **pipe_slot, const DemodStateSoA &st, 
 #ifndef MDEMOD_PIPE_MAX_QUEUED
 #define MDEMOD_PIPE_MAX_QUEUED 2
 #endif
-		if (k >= MDEMOD_PIPE_MAX_QUEUED) PIPE_TRY(hipEventSynchronize(p->slot[(k - MDEMOD_PIPE_MAX_QUEUED) % kSlots].ev_in));
+		if (k >= MDEMOD_PIPE_MAX_QUEUED) HIP_TRY(hipEventSynchronize(p->slot[(k - MDEMOD_PIPE_MAX_QUEUED) % kSlots].ev_in));
 #ifdef MDEMOD_PIPE_TRACE
 		tr_enq_at[k] = (tr_now() - tr_t0) * 1e3;
 		(void)hipEventRecord(tr_e0[k], p->s_in);
@@ -508,12 +498,12 @@ mdemod_hostpipe_run(mdemod_ctx *ctx, void **pipe_slot, const DemodStateSoA &st, 
 			/* every stream's piece is [lo, lo + cnt) of its row: device rows at the ring's own pitch (8-sample multiples, h_off) */
 			const uint32_t lo = sub_lo(0, k), cnt = sl.h_cnt[0];
 			const size_t dev_pitch = ns > 1 ? static_cast<size_t>(sl.h_off[1] - sl.h_off[0]) * sb : static_cast<size_t>(cnt) * sb;
-			if (cnt) PIPE_TRY(hipMemcpy2DAsync(sl.d_iq, dev_pitch, static_cast<const unsigned char *>(iq_host[0]) + static_cast<size_t>(lo) * sb, row_stride,
+			if (cnt) HIP_TRY(hipMemcpy2DAsync(sl.d_iq, dev_pitch, static_cast<const unsigned char *>(iq_host[0]) + static_cast<size_t>(lo) * sb, row_stride,
 			                                   static_cast<size_t>(cnt) * sb, ns, hipMemcpyHostToDevice, p->s_in));
 		} else if (!direct_k) {
 			memcpy(sl.h_iq + meta_at, sl.h_off, sizeof(uint64_t) * ns);
 			memcpy(sl.h_iq + meta_at + sizeof(uint64_t) * ns, sl.h_cnt, sizeof(uint32_t) * ns);
-			PIPE_TRY(hipMemcpyAsync(sl.d_iq, sl.h_iq, meta_at + meta_bytes, hipMemcpyHostToDevice, p->s_in));
+			HIP_TRY(hipMemcpyAsync(sl.d_iq, sl.h_iq, meta_at + meta_bytes, hipMemcpyHostToDevice, p->s_in));
 		}
 #ifdef MDEMOD_PIPE_TRACE
 		(void)hipEventRecord(tr_e1[k], p->s_in);
@@ -521,17 +511,17 @@ mdemod_hostpipe_run(mdemod_ctx *ctx, void **pipe_slot, const DemodStateSoA &st, 
 #ifdef MDEMOD_PIPE_TRACE_LIGHT
 		if (k + 1 == K) (void)hipEventRecord(lt_last_in, p->s_in);
 #endif
-		PIPE_TRY(hipEventRecord(sl.ev_in, p->s_in)); sl.used_in = true;
+		HIP_TRY(hipEventRecord(sl.ev_in, p->s_in)); sl.used_in = true;
 
 		/* ---- kernel: after the copy-in, and after the copy-out that last read this slot's device output ---- */
-		PIPE_TRY(hipStreamWaitEvent(p->s_cmp, sl.ev_in, 0));
-		if (sl.used_out) PIPE_TRY(hipStreamWaitEvent(p->s_cmp, sl.ev_out, 0));
+		HIP_TRY(hipStreamWaitEvent(p->s_cmp, sl.ev_in, 0));
+		if (sl.used_out) HIP_TRY(hipStreamWaitEvent(p->s_cmp, sl.ev_out, 0));
 		sl.cap = cap; sl.pitch = pitch;
 		const uint64_t *k_off = reinterpret_cast<const uint64_t *>(sl.d_iq + meta_at);
 		const uint32_t *k_cnt = reinterpret_cast<const uint32_t *>(sl.d_iq + meta_at + sizeof(uint64_t) * ns);
 		if (direct_k) {
 			/* (after the kernel that last read this slot's arrays: the compute stream is in order) */
-			PIPE_TRY(mdemod_launch_fill_uniform_rows(sl.d_off, sl.d_cnt, ns > 1 ? sl.h_off[1] - sl.h_off[0] : 0, sl.h_cnt[0], ns, p->s_cmp));
+			HIP_TRY(mdemod_launch_fill_uniform_rows(sl.d_off, sl.d_cnt, ns > 1 ? sl.h_off[1] - sl.h_off[0] : 0, sl.h_cnt[0], ns, p->s_cmp));
 			k_off = sl.d_off; k_cnt = sl.d_cnt;
 		}
 #ifdef MDEMOD_PIPE_TRACE
@@ -556,19 +546,19 @@ mdemod_hostpipe_run(mdemod_ctx *ctx, void **pipe_slot, const DemodStateSoA &st, 
 #ifdef MDEMOD_PIPE_TRACE
 		if (!(tr_skip & (1 | 8)))
 #endif
-		PIPE_TRY(mdemod_launch_compact_rows(sl.d_soft, cap, zc_out ? sl.h_soft : sl.d_pack, pitch, st.sym_this_call, ns, p->s_cmp));
+		HIP_TRY(mdemod_launch_compact_rows(sl.d_soft, cap, zc_out ? sl.h_soft : sl.d_pack, pitch, st.sym_this_call, ns, p->s_cmp));
 #ifdef MDEMOD_PIPE_COUNTS_BY_COPY
-		PIPE_TRY(hipMemcpyAsync(sl.h_prod, st.sym_this_call, sizeof(uint32_t) * ns, hipMemcpyDeviceToHost, p->s_cmp));
-		PIPE_TRY(hipMemcpyAsync(sl.h_ev, st.ev_this_call, sizeof(uint32_t) * ns, hipMemcpyDeviceToHost, p->s_cmp));
+		HIP_TRY(hipMemcpyAsync(sl.h_prod, st.sym_this_call, sizeof(uint32_t) * ns, hipMemcpyDeviceToHost, p->s_cmp));
+		HIP_TRY(hipMemcpyAsync(sl.h_ev, st.ev_this_call, sizeof(uint32_t) * ns, hipMemcpyDeviceToHost, p->s_cmp));
 #endif
 		/* (only the events there are: the whole list is 512 bytes per stream - 8 MB and 0.46 ms of blit kernel per sub-block at 16 384
 		   streams, the last of them in the call's tail; r05) */
 #ifdef MDEMOD_PIPE_COUNTS_BY_COPY
-		if (K > 1) PIPE_TRY(mdemod_launch_copy_events(st, sl.d_events, ns, nullptr, nullptr, p->s_cmp));
+		if (K > 1) HIP_TRY(mdemod_launch_copy_events(st, sl.d_events, ns, nullptr, nullptr, p->s_cmp));
 #else
 		/* ... and the launch's two counters per stream into the slot's pinned arrays by the same kernel: as copies they sat in a copy
 		   engine's queue until the kernel was through, and the runtime may put the next 2-D copy-in behind them (r05) */
-		PIPE_TRY(mdemod_launch_copy_events(st, sl.d_events, ns, sl.h_prod, sl.h_ev, p->s_cmp));
+		HIP_TRY(mdemod_launch_copy_events(st, sl.d_events, ns, sl.h_prod, sl.h_ev, p->s_cmp));
 #endif
 #ifdef MDEMOD_PIPE_TRACE
 		(void)hipEventRecord(tr_k1[k], p->s_cmp);
@@ -576,17 +566,17 @@ mdemod_hostpipe_run(mdemod_ctx *ctx, void **pipe_slot, const DemodStateSoA &st, 
 #ifdef MDEMOD_PIPE_TRACE_LIGHT
 		if (k + 1 == K) (void)hipEventRecord(lt_last_k, p->s_cmp);
 #endif
-		PIPE_TRY(hipEventRecord(sl.ev_k, p->s_cmp)); sl.used_k = true;
+		HIP_TRY(hipEventRecord(sl.ev_k, p->s_cmp)); sl.used_k = true;
 		/* ---- D2H of the nominal-pitch copy ---- */
-		PIPE_TRY(hipStreamWaitEvent(p->s_out, sl.ev_k, 0));
+		HIP_TRY(hipStreamWaitEvent(p->s_out, sl.ev_k, 0));
 #ifdef MDEMOD_PIPE_TRACE
 		if (!(tr_skip & 2))
 #endif
-		if (!zc_out) PIPE_TRY(hipMemcpyAsync(sl.h_soft, sl.d_pack, pack_bytes, hipMemcpyDeviceToHost, p->s_out));
+		if (!zc_out) HIP_TRY(hipMemcpyAsync(sl.h_soft, sl.d_pack, pack_bytes, hipMemcpyDeviceToHost, p->s_out));
 #ifdef MDEMOD_PIPE_TRACE
 		(void)hipEventRecord(tr_o1[k], p->s_out);
 #endif
-		PIPE_TRY(hipEventRecord(sl.ev_out, p->s_out)); sl.used_out = true;
+		HIP_TRY(hipEventRecord(sl.ev_out, p->s_out)); sl.used_out = true;
 		/* ---- hand sub-block k-2 back to the caller while k-1 is under the kernel and k on the link (its copy-out is done: no wait) ---- */
 		if (k >= 2) { TR(tr_unpack, rc = unpack(p->slot[(k - 2) % kSlots])); if (rc) return rc; }
 	}
@@ -620,13 +610,13 @@ mdemod_hostpipe_run(mdemod_ctx *ctx, void **pipe_slot, const DemodStateSoA &st, 
 #endif
 	/* ---- "this call" counters := totals over the sub-blocks ---- */
 	if (K > 1) {
-		PIPE_TRY(hipMemcpyAsync(st.sym_this_call, produced.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice, p->s_cmp));
-		PIPE_TRY(hipMemcpyAsync(st.ev_this_call, events.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice, p->s_cmp));
+		HIP_TRY(hipMemcpyAsync(st.sym_this_call, produced.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice, p->s_cmp));
+		HIP_TRY(hipMemcpyAsync(st.ev_this_call, events.data(), sizeof(uint32_t) * ns, hipMemcpyHostToDevice, p->s_cmp));
 		if (!ev_store.empty())
-			PIPE_TRY(hipMemcpyAsync(st.events, ev_store.data(), ev_store.size() * sizeof(mdemod_lock_event), hipMemcpyHostToDevice, p->s_cmp));
+			HIP_TRY(hipMemcpyAsync(st.events, ev_store.data(), ev_store.size() * sizeof(mdemod_lock_event), hipMemcpyHostToDevice, p->s_cmp));
 	}
-	PIPE_TRY(hipStreamSynchronize(p->s_cmp));
-	PIPE_TRY(hipStreamSynchronize(p->s_out));
+	HIP_TRY(hipStreamSynchronize(p->s_cmp));
+	HIP_TRY(hipStreamSynchronize(p->s_out));
 	if (n_symbols) for (uint32_t s = 0; s < ns; s++) n_symbols[s] = produced[s];
 	return result;
 }

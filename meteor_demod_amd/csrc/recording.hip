@@ -35,7 +35,7 @@
 #include <thread>
 #include <vector>
 
-#include "mdemod_internal_api.h"
+#include "hip_host.h"
 
 namespace {
 
@@ -521,32 +521,20 @@ assemble_kernel(const TileCopy *tiles, int8_t *out)
 
 /* ---- host side ----------------------------------------------------------------------------- */
 
-struct DevMem {                      /* frees everything on scope exit */
-	std::vector<void *> p;
-	~DevMem() { for (void *q : p) (void)hipFree(q); }
-	template <typename T> int alloc(T **out, size_t n) {
-		void *q = nullptr;
-		if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return MDEMOD_ERR_NOMEM;
-		p.push_back(q); *out = static_cast<T *>(q); return MDEMOD_OK;
-	}
-};
-
 struct Ctx {                         /* owns a demodulator context */
 	mdemod_ctx *c = nullptr;
 	~Ctx() { if (c) mdemod_destroy(c); }
 };
 
 #define TRY(expr) do { int rc_ = (expr); if (rc_ < 0) return rc_; } while (0)
-#define HTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { mdm_note_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); (void)hipGetLastError(); return e_ == hipErrorOutOfMemory ? MDEMOD_ERR_NOMEM : MDEMOD_ERR_HIP; } } while (0)
-
 template <typename T>
 int
-upload(DevMem &m, const std::vector<T> &h, T **dev, hipStream_t st)
+upload(MdmDevMem &m, const std::vector<T> &h, T **dev, hipStream_t st)
 {
 	TRY(m.alloc(dev, h.size()));
 	if (!h.empty()) {
-		HTRY(hipMemcpyAsync(*dev, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
-		HTRY(hipStreamSynchronize(st));          /* h is pageable and may die with the caller's scope: small tables, wait here */
+		HIP_TRY(hipMemcpyAsync(*dev, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipStreamSynchronize(st));          /* h is pageable and may die with the caller's scope: small tables, wait here */
 	}
 	return MDEMOD_OK;
 }
@@ -566,7 +554,7 @@ counts_of(mdemod_ctx *c, uint32_t n, std::vector<uint32_t> &out, hipStream_t st,
 }
 
 int
-run_match(DevMem &m, const std::vector<TailPair> &pairs, int K, std::vector<int32_t> &shift, std::vector<int32_t> &rot,
+run_match(MdmDevMem &m, const std::vector<TailPair> &pairs, int K, std::vector<int32_t> &shift, std::vector<int32_t> &rot,
           std::vector<int32_t> &weak, hipStream_t st, int mode = 0)
 {
 	const size_t T = pairs.size();
@@ -574,14 +562,14 @@ run_match(DevMem &m, const std::vector<TailPair> &pairs, int K, std::vector<int3
 	TailPair *d_pairs; int32_t *d_out;
 	TRY(upload(m, pairs, &d_pairs, st));
 	TRY(m.alloc(&d_out, 3 * T));
-	HTRY(hipMemsetAsync(d_out, 0, 3 * T * sizeof(int32_t), st));
+	HIP_TRY(hipMemsetAsync(d_out, 0, 3 * T * sizeof(int32_t), st));
 	if (mode == 1) hipLaunchKernelGGL(match_rails_kernel, dim3((unsigned)T), dim3(64), 0, st, d_pairs, K, d_out + T, d_out + 2 * T);
 	else if (mode == 2) hipLaunchKernelGGL(match_heads_kernel, dim3((unsigned)T), dim3(64), 0, st, d_pairs, K, d_out, d_out + T, d_out + 2 * T);
 	else hipLaunchKernelGGL(match_kernel, dim3((unsigned)T), dim3(64), 0, st, d_pairs, K, d_out, d_out + T, d_out + 2 * T);
-	HTRY(hipGetLastError());
+	HIP_TRY(hipGetLastError());
 	std::vector<int32_t> h(3 * T);
-	HTRY(hipMemcpyAsync(h.data(), d_out, 3 * T * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-	HTRY(hipStreamSynchronize(st));
+	HIP_TRY(hipMemcpyAsync(h.data(), d_out, 3 * T * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
 	shift.assign(h.begin(), h.begin() + T); rot.assign(h.begin() + T, h.begin() + 2 * T); weak.assign(h.begin() + 2 * T, h.end());
 	return MDEMOD_OK;
 }
@@ -671,17 +659,15 @@ try { MDEMOD_API_ENTER
 	const float rad_per_hz = static_cast<float>(2 * 3.141592653589793 / (symrate * nco));
 	/* chirp in rad per NCO step per sample -> carrier rad per sample^2 (x nco * symrate / fs) -> turns of z^4 per sample^2 (/ pi) */
 	const float chirp_scale = static_cast<float>(nco * symrate / fs / 3.141592653589793);
-#define LAUNCH_LINE(F) do { \
-		HTRY(hipFuncSetAttribute(reinterpret_cast<const void *>(carrier_line_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds))); \
-		hipLaunchKernelGGL(carrier_line_kernel<F>, grid, dim3(1024), lds, st, iq_dev, n_samples, starts_dev, chirp_dev, chirp_scale, log2_nf, decim, pre, kmax, \
-		                   hz_per_bin_over4, rad_per_hz, freq_dev, quality_dev); } while (0)
+#define LAUNCH_LINE(F) \
+	HIP_TRY(mdm_launch(carrier_line_kernel<F>, grid, dim3(1024), lds, st, iq_dev, n_samples, starts_dev, chirp_dev, chirp_scale, log2_nf, decim, pre, kmax, \
+	                   hz_per_bin_over4, rad_per_hz, freq_dev, quality_dev))
 	switch (params->bps) {
 	case 16: LAUNCH_LINE(16); break;
 	case 8:  LAUNCH_LINE(8); break;
 	default: LAUNCH_LINE(32); break;
 	}
 #undef LAUNCH_LINE
-	HTRY(hipGetLastError());
 	return MDEMOD_OK;
 } MDEMOD_API_CATCH
 
@@ -717,17 +703,15 @@ try { MDEMOD_API_ENTER
 	const double chirp_scale = nco * symrate / fs / (2 * 3.141592653589793);
 	const double t_freq_scale = 2 * 3.141592653589793 / params->interp_factor;
 	const size_t lds = (static_cast<size_t>(1) << log2_nf) * sizeof(float2) * (params->oqpsk ? 2 : 1);
-#define LAUNCH_CLK(F) do { \
-		HTRY(hipFuncSetAttribute(reinterpret_cast<const void *>(clock_line_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds))); \
-		hipLaunchKernelGGL(clock_line_kernel<F>, dim3(n_windows), dim3(1024), lds, st, iq_dev, n_samples, starts_dev, carrier_dev, chirp_dev, \
-		                   carrier_scale, chirp_scale, params->oqpsk ? 1 : 0, log2_nf, decim, kmax, knoise, f_nom, t_freq_scale, t_freq_dev, quality_dev); } while (0)
+#define LAUNCH_CLK(F) \
+	HIP_TRY(mdm_launch(clock_line_kernel<F>, dim3(n_windows), dim3(1024), lds, st, iq_dev, n_samples, starts_dev, carrier_dev, chirp_dev, \
+	                   carrier_scale, chirp_scale, params->oqpsk ? 1 : 0, log2_nf, decim, kmax, knoise, f_nom, t_freq_scale, t_freq_dev, quality_dev))
 	switch (params->bps) {
 	case 16: LAUNCH_CLK(16); break;
 	case 8:  LAUNCH_CLK(8); break;
 	default: LAUNCH_CLK(32); break;
 	}
 #undef LAUNCH_CLK
-	HTRY(hipGetLastError());
 	return MDEMOD_OK;
 } MDEMOD_API_CATCH
 
@@ -807,7 +791,7 @@ run_pilot(const mdemod_params *params, const mdemod_recording_opts &o, const voi
 	Ctx pilot;
 	TRY(mdemod_create(&pp, &pilot.c));
 	uint64_t pos = 0, nsym = 0; bool have_lock = false, lost_lock = false; uint64_t locked_at = 0;
-	DevMem est_mem; unsigned char *d_est = nullptr; unsigned false_checks = 0; bool waiting_for_genuine = false;
+	MdmDevMem est_mem; unsigned char *d_est = nullptr; unsigned false_checks = 0; bool waiting_for_genuine = false;
 	std::vector<PilotBlock> &pilot_blocks = po.blocks;
 	mdemod_stream_state &seed = po.seed;
 	memset(&seed, 0, sizeof(seed));
@@ -852,13 +836,13 @@ run_pilot(const mdemod_params *params, const mdemod_recording_opts &o, const voi
 					if (!d_est) TRY(est_mem.alloc(&d_est, 32));
 					const uint32_t win = mdemod_carrier_window_samples(params, static_cast<uint32_t>(std::min(262144.0, 20536.0 * params->samplerate / params->symrate)));
 					const uint64_t w0 = pos > win ? pos - win : 0;
-					HTRY(hipMemcpyAsync(d_est, &w0, sizeof(w0), hipMemcpyHostToDevice, st));
-					HTRY(hipStreamSynchronize(st));
+					HIP_TRY(hipMemcpyAsync(d_est, &w0, sizeof(w0), hipMemcpyHostToDevice, st));
+					HIP_TRY(hipStreamSynchronize(st));
 					float *d_f = reinterpret_cast<float *>(d_est + 8), *d_q = reinterpret_cast<float *>(d_est + 16);
 					TRY(mdemod_estimate_carrier(params, iq_dev, std::min<uint64_t>(n_samples, pos), reinterpret_cast<const uint64_t *>(d_est), 1, win, d_f, d_q, st));
 					float fq[4];
-					HTRY(hipMemcpyAsync(fq, d_est + 8, sizeof(fq), hipMemcpyDeviceToHost, st));
-					HTRY(hipStreamSynchronize(st));
+					HIP_TRY(hipMemcpyAsync(fq, d_est + 8, sizeof(fq), hipMemcpyDeviceToHost, st));
+					HIP_TRY(hipStreamSynchronize(st));
 					const double thr = 2 * kPi * 100.0 / (static_cast<double>(params->symrate) * (params->oqpsk ? 2 : 1));     /* genuine locks are within 40 Hz by then, false ones start at 160 */
 					genuine = !(fq[2] >= 8.0f && std::fabs(static_cast<double>(seed.pll_freq) - static_cast<double>(fq[0])) > thr);
 					waiting_for_genuine = !genuine;
@@ -892,7 +876,7 @@ struct Stitcher {
 	/* the plan: tile i emits [E_i, E_i + len_i), its stream starts at s0_i and runs acq_i + frm_i + stl_i samples before that */
 	uint64_t B = 0, A = 0, KP = 0, WS = 0; size_t T = 0;
 	std::vector<uint64_t> E, len, s0, acq, frm, stl, q;
-	mdemod_params bp; Ctx bank, saved; DevMem mem; float consts[8]; double fmax = 0, tau_pll = 0;
+	mdemod_params bp; Ctx bank, saved; MdmDevMem mem; float consts[8]; double fmax = 0, tau_pll = 0;
 	/* estimates: carrier (centre, fbar, slope) and clock lines (ge_*) on grids of their own, taken while the head runs; per tile
 	   the clock seed and the carrier's local slope */
 	std::vector<double> tclk, centre, fbar, slope, slope_tile; int nfft = 0; float min_quality = 8.0f; std::vector<uint64_t> wstart; double f_pilot_target = 0;
@@ -937,9 +921,9 @@ struct Stitcher {
 			f0[i] = i == 0 ? seed.pll_freq : static_cast<float>(f_seed(i, static_cast<double>(s0[i] + (at_acquired ? acq[i] : 0))));
 			ud[i] = i == 0 ? seed.pll_updown : (slope_tile[i] >= 0 ? 1 : -1);
 		}
-		HTRY(hipMemcpyAsync(d_f0, f0.data(), T * sizeof(float), hipMemcpyHostToDevice, st));
-		HTRY(hipMemcpyAsync(d_ud, ud.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-		HTRY(hipStreamSynchronize(st));
+		HIP_TRY(hipMemcpyAsync(d_f0, f0.data(), T * sizeof(float), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d_ud, ud.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipStreamSynchronize(st));
 		return mdemod_set_carrier_seeds(bank.c, d_f0, d_ud, st);
 	}
 	/* ---- launches ------------------------------------------------------------------------------------------- */
@@ -953,7 +937,7 @@ struct Stitcher {
 		TRY(upload(mem, off, &d_off, st));
 		TRY(upload(mem, c32, &d_cnt, st));
 			TRY(mdemod_process_device(bank.c, iq_dev, d_off, d_cnt, soft, stride, discard ? 0u : static_cast<uint32_t>(stride), st));
-		if (discard) HTRY(hipStreamSynchronize(st));
+		if (discard) HIP_TRY(hipStreamSynchronize(st));
 		else TRY(counts_of(bank.c, static_cast<uint32_t>(T), produced, st, status_out));
 		for (uint64_t c : cnt) rep->samples_demodulated += c;
 		return MDEMOD_OK;
@@ -1081,7 +1065,7 @@ struct Stitcher {
 	   integrator needs 8 000 symbols per e-fold to make that up).  The clock is smooth: every tile reads a straight line through
 	   the estimates around it (estimate_clocks).  OQPSK's line pair sits at twice the carrier +- the rate: it is looked for around
 	   the carrier curve, or - without one - around `carrier_word` (the head's). ---- */
-	int clock_lines(hipStream_t es, DevMem &emem, float carrier_word)
+	int clock_lines(hipStream_t es, MdmDevMem &emem, float carrier_word)
 	{
 		if (o.clock_seed == 0 && n_samples >= 4096) {
 			uint32_t wc = 4096;
@@ -1107,9 +1091,9 @@ struct Stitcher {
 			TRY(emem.alloc(&d_tfq, Tc)); TRY(emem.alloc(&d_cq, Tc));
 			TRY(mdemod_estimate_clock(params, iq_dev, n_samples, d_cst, d_cf, d_cc, static_cast<uint32_t>(Tc), wc, d_tfq, d_cq, es));
 			ge_th.assign(Tc, 0.0f); ge_cq.assign(Tc, 0.0f);
-			HTRY(hipMemcpyAsync(ge_th.data(), d_tfq, Tc * sizeof(float), hipMemcpyDeviceToHost, es));
-			HTRY(hipMemcpyAsync(ge_cq.data(), d_cq, Tc * sizeof(float), hipMemcpyDeviceToHost, es));
-			HTRY(hipStreamSynchronize(es));
+			HIP_TRY(hipMemcpyAsync(ge_th.data(), d_tfq, Tc * sizeof(float), hipMemcpyDeviceToHost, es));
+			HIP_TRY(hipMemcpyAsync(ge_cq.data(), d_cq, Tc * sizeof(float), hipMemcpyDeviceToHost, es));
+			HIP_TRY(hipStreamSynchronize(es));
 			ge_wc = wc;
 		}
 		return MDEMOD_OK;
@@ -1123,16 +1107,16 @@ struct Stitcher {
 	 * (mdemod_estimate_clock) of the estimator's longest windows (2^18 samples: 5e-8 of the rate), side by side as well. */
 	int estimate_grid()
 	{
-		(void)hipGetLastError(); HTRY(hipSetDevice(params->device));      /* (what an earlier call left pending is not this call's: demod_api.cpp select_device) */
-		struct OwnStream { hipStream_t s = nullptr; ~OwnStream() { if (s) (void)hipStreamDestroy(s); } } own;
+		TRY(mdm_select_device(params->device));
+		MdmStream own;
 		{
 			int least = 0, greatest = 0;                          /* behind the head's launches in the queues */
 			(void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-			HTRY(hipStreamCreateWithPriority(&own.s, hipStreamNonBlocking, least));
+			HIP_TRY(hipStreamCreateWithPriority(&own.s, hipStreamNonBlocking, least));
 		}
 		hipStream_t es = own.s;
-		if (input_ready.ev) HTRY(hipStreamWaitEvent(es, input_ready.ev, 0));
-		DevMem emem;
+		if (input_ready.ev) HIP_TRY(hipStreamWaitEvent(es, input_ready.ev, 0));
+		MdmDevMem emem;
 		if (need) (*need)(n_samples);                          /* the host-buffer entry is still copying the recording in */
 		nfft = static_cast<int>(mdemod_carrier_window_samples(params, static_cast<uint32_t>(std::min(262144.0, 20536.0 * osf))));
 		const uint64_t W = static_cast<uint64_t>(nfft);
@@ -1169,21 +1153,21 @@ struct Stitcher {
 					for (size_t i = 0; i < G; i++) if (std::fabs(chirp[i]) * nfft > 0.1 * bin) sel.push_back(i);
 					if (sel.empty()) break;
 					for (size_t k = 0; k < sel.size(); k++) { wsel[k] = wstart[sel[k]]; csel[k] = chirp[sel[k]]; }
-					HTRY(hipMemcpyAsync(d_chirp, csel.data(), sel.size() * sizeof(float), hipMemcpyHostToDevice, es));
-					HTRY(hipMemcpyAsync(d_starts_sel, wsel.data(), sel.size() * sizeof(uint64_t), hipMemcpyHostToDevice, es));
-					HTRY(hipStreamSynchronize(es));
+					HIP_TRY(hipMemcpyAsync(d_chirp, csel.data(), sel.size() * sizeof(float), hipMemcpyHostToDevice, es));
+					HIP_TRY(hipMemcpyAsync(d_starts_sel, wsel.data(), sel.size() * sizeof(uint64_t), hipMemcpyHostToDevice, es));
+					HIP_TRY(hipStreamSynchronize(es));
 					TRY(mdemod_estimate_carrier_chirp(params, iq_dev, n_samples, d_starts_sel, d_chirp, static_cast<uint32_t>(sel.size()),
 					                                  static_cast<uint32_t>(nfft), d_freq, d_qual, es));
-					HTRY(hipMemcpyAsync(fsel.data(), d_freq, sel.size() * sizeof(float), hipMemcpyDeviceToHost, es));
-					HTRY(hipMemcpyAsync(qsel.data(), d_qual, sel.size() * sizeof(float), hipMemcpyDeviceToHost, es));
-					HTRY(hipStreamSynchronize(es));
+					HIP_TRY(hipMemcpyAsync(fsel.data(), d_freq, sel.size() * sizeof(float), hipMemcpyDeviceToHost, es));
+					HIP_TRY(hipMemcpyAsync(qsel.data(), d_qual, sel.size() * sizeof(float), hipMemcpyDeviceToHost, es));
+					HIP_TRY(hipStreamSynchronize(es));
 					for (size_t k = 0; k < sel.size(); k++) { fh[sel[k]] = fsel[k]; qh[sel[k]] = qsel[k]; }
 				} else {
 					TRY(mdemod_estimate_carrier_chirp(params, iq_dev, n_samples, d_starts, nullptr, static_cast<uint32_t>(G),
 					                                  static_cast<uint32_t>(nfft), d_freq, d_qual, es));
-					HTRY(hipMemcpyAsync(fh.data(), d_freq, G * sizeof(float), hipMemcpyDeviceToHost, es));
-					HTRY(hipMemcpyAsync(qh.data(), d_qual, G * sizeof(float), hipMemcpyDeviceToHost, es));
-					HTRY(hipStreamSynchronize(es));
+					HIP_TRY(hipMemcpyAsync(fh.data(), d_freq, G * sizeof(float), hipMemcpyDeviceToHost, es));
+					HIP_TRY(hipMemcpyAsync(qh.data(), d_qual, G * sizeof(float), hipMemcpyDeviceToHost, es));
+					HIP_TRY(hipStreamSynchronize(es));
 				}
 				if (dbg) fprintf(stderr, "[recording] carrier pass %d: %zu of %zu windows of %d\n", pass, pass ? sel.size() : G, G, nfft);
 				/* windows without a clear line (fade, interference) take their good neighbours' estimate, interpolated over time;
@@ -1306,9 +1290,9 @@ struct Stitcher {
 		   needs a seed per tile, and only then is the recording read once more for its power */
 		const bool slow_agc = 6.0 * static_cast<double>(seed.agc_gain) / (1e-4 * 190.0) > 0.25 * static_cast<double>(A) / osf;
 		if (T > 1 && !slow_agc) {
-			HTRY(hipMemcpyAsync(d_gain, gains.data(), T * sizeof(float), hipMemcpyHostToDevice, st));
-			HTRY(hipMemcpyAsync(d_tf, tf.data(), T * sizeof(float), hipMemcpyHostToDevice, st));
-			HTRY(hipStreamSynchronize(st));
+			HIP_TRY(hipMemcpyAsync(d_gain, gains.data(), T * sizeof(float), hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemcpyAsync(d_tf, tf.data(), T * sizeof(float), hipMemcpyHostToDevice, st));
+			HIP_TRY(hipStreamSynchronize(st));
 			TRY(put_carrier_seeds(false));
 		}
 		if (T > 1 && slow_agc) {
@@ -1323,17 +1307,17 @@ struct Stitcher {
 			TRY(upload(mem, ws, &d_ws, st));
 			TRY(upload(mem, wl, &d_wl, st));
 			TRY(mem.alloc(&d_wp, ws.size()));
-			HTRY(hipStreamSynchronize(st));
+			HIP_TRY(hipStreamSynchronize(st));
 			const dim3 grid(static_cast<unsigned>(ws.size()));
 			switch (params->bps) {
 			case 16: hipLaunchKernelGGL(window_power_kernel<16>, grid, dim3(256), 0, st, iq_dev, d_ws, d_wl, d_wp); break;
 			case 8:  hipLaunchKernelGGL(window_power_kernel<8>, grid, dim3(256), 0, st, iq_dev, d_ws, d_wl, d_wp); break;
 			default: hipLaunchKernelGGL(window_power_kernel<32>, grid, dim3(256), 0, st, iq_dev, d_ws, d_wl, d_wp); break;
 			}
-			HTRY(hipGetLastError());
+			HIP_TRY(hipGetLastError());
 			std::vector<float> wp(ws.size());
-			HTRY(hipMemcpyAsync(wp.data(), d_wp, wp.size() * sizeof(float), hipMemcpyDeviceToHost, st));
-			HTRY(hipStreamSynchronize(st));
+			HIP_TRY(hipMemcpyAsync(wp.data(), d_wp, wp.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipStreamSynchronize(st));
 			std::vector<double> blk_gain(nb), blk_power(nb), blk_syms(nb);
 			for (size_t j = 0; j < nb; j++) {
 				const PilotBlock &pb = po.blocks[b0 + j];
@@ -1350,9 +1334,9 @@ struct Stitcher {
 				const size_t back = static_cast<size_t>((E[i] - s0[i] + B - 1) / B);
 				gains[i] = static_cast<float>(gE[i > back ? i - back : 0]);
 			}
-			HTRY(hipMemcpyAsync(d_gain, gains.data(), T * sizeof(float), hipMemcpyHostToDevice, st));
-			HTRY(hipMemcpyAsync(d_tf, tf.data(), T * sizeof(float), hipMemcpyHostToDevice, st));
-			HTRY(hipStreamSynchronize(st));
+			HIP_TRY(hipMemcpyAsync(d_gain, gains.data(), T * sizeof(float), hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemcpyAsync(d_tf, tf.data(), T * sizeof(float), hipMemcpyHostToDevice, st));
+			HIP_TRY(hipStreamSynchronize(st));
 			TRY(mdemod_set_gain_seeds(bank.c, d_gain, st));
 			TRY(put_carrier_seeds(false));
 		}
@@ -1450,8 +1434,8 @@ struct Stitcher {
 		for (int round = 0; round < 2; round++) {
 			std::vector<int32_t> qt(T);
 			for (size_t i = 0; i < T; i++) qt[i] = run[i] ? (4 - state_rot[i]) & 3 : 0;
-			HTRY(hipMemcpyAsync(d_rot, qt.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-			HTRY(hipStreamSynchronize(st));
+			HIP_TRY(hipMemcpyAsync(d_rot, qt.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+			HIP_TRY(hipStreamSynchronize(st));
 			TRY(mdemod_rotate_carrier(bank.c, d_rot, st));
 			auto masked = [&](const std::vector<uint64_t> &c) { std::vector<uint64_t> m(T); for (size_t i = 0; i < T; i++) m[i] = run[i] ? c[i] : 0; return m; };
 			std::vector<mdemod_status> stat;
@@ -1573,8 +1557,8 @@ struct Stitcher {
 				std::vector<int32_t> qt(T, 0);
 				std::vector<uint64_t> c_stl(T, 0), c_body(T, 0), c_post(T, 0), o_post(T, 0);
 				for (size_t j : preds) { qt[j] = (4 - state_rot[j]) & 3; c_stl[j] = stl[j]; c_body[j] = len[j] + len[j + 1]; o_post[j] = ends[j + 1]; c_post[j] = post_len[j + 1]; }
-				HTRY(hipMemcpyAsync(d_rot, qt.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
-				HTRY(hipStreamSynchronize(st));
+				HIP_TRY(hipMemcpyAsync(d_rot, qt.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, st));
+				HIP_TRY(hipStreamSynchronize(st));
 				TRY(mdemod_rotate_carrier(bank.c, d_rot, st));
 				std::vector<uint32_t> cnt_fix;
 				TRY(launch(stl_off, c_stl, soft_pre, cap_lead, cnt_tmp, nullptr, true));
@@ -1675,8 +1659,8 @@ struct Stitcher {
 		/* few tiles: several blocks per tile, so that the copy still fills the GPU */
 		const unsigned slices = static_cast<unsigned>(std::min<uint64_t>(64, std::max<uint64_t>(1, 4096 / T)));
 		hipLaunchKernelGGL(assemble_kernel, dim3(static_cast<unsigned>(T), slices), dim3(256), 0, st, d_copies, soft_dev);
-		HTRY(hipGetLastError());
-		HTRY(hipStreamSynchronize(st));
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(st));
 		mark("assembled");
 		rep->n_symbols = out_pos;
 		rep->tiles_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_tiles).count();
@@ -1686,8 +1670,8 @@ struct Stitcher {
 	int run_all()
 	{
 		TRY(prepare());
-		HTRY(hipEventCreateWithFlags(&input_ready.ev, hipEventDisableTiming));
-		HTRY(hipEventRecord(input_ready.ev, st));
+		HIP_TRY(hipEventCreateWithFlags(&input_ready.ev, hipEventDisableTiming));
+		HIP_TRY(hipEventRecord(input_ready.ev, st));
 		try {
 			/* (a thread's exception is nobody's to catch: std::terminate.  The function-try-blocks of the entries cover the calling thread only) */
 			est.t = std::thread([this]() { try { est.rc = estimate_grid(); } catch (...) { est.rc = MDEMOD_ERR_NOMEM; } });    /* joined by estimate_carriers, or by ~EstThread on an early return */
@@ -1758,16 +1742,16 @@ try { MDEMOD_API_ENTER
 	auto mark = [&](const char *what) {
 		if (dbg) fprintf(stderr, "[recording host] %8.2f ms  %s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_in).count() * 1e3, what);
 	};
-	(void)hipGetLastError(); HTRY(hipSetDevice(params->device));      /* (what an earlier call left pending is not this call's: demod_api.cpp select_device) */
+	TRY(mdm_select_device(params->device));
 	mark("device set");
 	const size_t sb = 2 * static_cast<size_t>(params->bps) / 8;
-	DevMem mem;
+	MdmDevMem mem;
 	unsigned char *d_iq; int8_t *d_soft;
 	TRY(mem.alloc(&d_iq, static_cast<size_t>(n_samples) * sb));
 	TRY(mem.alloc(&d_soft, static_cast<size_t>(soft_cap_symbols) * 2));
 	mark("buffers allocated");
 	const uint64_t head = std::min<uint64_t>(n_samples, 1u << 20);
-	if (head) HTRY(hipMemcpy(d_iq, iq_host, static_cast<size_t>(head) * sb, hipMemcpyHostToDevice));
+	if (head) HIP_TRY(hipMemcpy(d_iq, iq_host, static_cast<size_t>(head) * sb, hipMemcpyHostToDevice));
 	mark("head copied");
 	std::atomic<uint64_t> there{head};
 	std::atomic<int> copy_failed{0};
@@ -1794,16 +1778,16 @@ try { MDEMOD_API_ENTER
 	};
 	/* a stream of this call's own: on the null stream the calls of several host threads (the C host's --jobs) would run one
 	   kernel after the other, serial heads included */
-	struct OwnStream { hipStream_t s = nullptr; ~OwnStream() { if (s) (void)hipStreamDestroy(s); } } own;
-	HTRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+	MdmStream own;
+	HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
 	const int rc = demodulate_recording_impl(params, opts, d_iq, n_samples, d_soft, soft_cap_symbols, rep, own.s, &need);
 	if (copier.t.joinable()) copier.t.join();
 	mark("demodulated");
 	if (copy_failed.load()) return MDEMOD_ERR_HIP;
 	TRY(rc);
 	if (rep->n_symbols) {
-		HTRY(hipMemcpyAsync(soft_host, d_soft, static_cast<size_t>(rep->n_symbols) * 2, hipMemcpyDeviceToHost, own.s));
-		HTRY(hipStreamSynchronize(own.s));
+		HIP_TRY(hipMemcpyAsync(soft_host, d_soft, static_cast<size_t>(rep->n_symbols) * 2, hipMemcpyDeviceToHost, own.s));
+		HIP_TRY(hipStreamSynchronize(own.s));
 	}
 	mark("symbols copied out");
 	return MDEMOD_OK;

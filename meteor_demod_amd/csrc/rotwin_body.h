@@ -243,11 +243,6 @@ rotwin_demod(const DemodLaunch &L)
 	}
 
 	__syncthreads();                                       /* coefficient rows + LUT visible */
-#ifdef ROT_EXP_PHASE             /* experiment (r06, NOTEBOOK R6.3): the waves of a block selected by ROT_EXP_PHASE_MASK start ROT_EXP_PHASE x 64 cycles late -
-                                    do two waves of a SIMD that are out of step (one in its FIR while the other is in its scalar stage) fill each other's bubbles?
-                                    Measured: no - offsets of 900 / 1 800 / 3 600 cycles on waves 4-7, odd waves or waves 2-3, 6-7: +-0.3 % on configs[1], -1 % on configs[2] (NOTEBOOK R6.3) */
-	if ((threadIdx.x >> 6) & ROT_EXP_PHASE_MASK) __builtin_amdgcn_s_sleep(ROT_EXP_PHASE);
-#endif
 
 	int rot = 0;                                           /* physical chunk that is logical chunk 0 (wave-uniform) */
 	/* OQPSK: demod.c:62-84 does half the work on the I-rail firing (state 1: one mixer product, no timing or Costas update, no
@@ -274,7 +269,8 @@ rotwin_demod(const DemodLaunch &L)
 	n_wave_max = __builtin_amdgcn_readfirstlane(n_wave_max);
 	const uint64_t guard64 = 4ull * (uint64_t)(n_wave_max + kBack) * (uint64_t)interp + 4096ull;
 	uint32_t guard = guard64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)guard64;
-#ifdef ROT_EXP_TIMING            /* experiment: where a wave's time goes (s_memtime between the stages; block 100, wave 0 prints) */
+#ifdef ROT_EXP_TIMING            /* experiment: where a wave's time goes (s_memtime between the stages; block 100, wave 0 prints):
+                                    tools/build_exp_rot.sh x "-DROT_EXP_TIMING", run by tools/pmc_shape.py - the stage clocks of profiles/r04_path_and_budget.md */
 	uint64_t tacc[5] = { 0, 0, 0, 0, 0 }, tlast = clock64();
 	uint32_t n_iter = 0, n_fir = 0, n_slide = 0, n_wslow = 0;
 #define ROT_TICK(i) do { const uint64_t t_ = clock64(); tacc[i] += t_ - tlast; tlast = t_; } while (0)
@@ -301,7 +297,7 @@ rotwin_demod(const DemodLaunch &L)
 		}
 		if (md_all(done)) break;
 		ROT_TICK(0);
-#ifdef ROT_EXP_TIMING
+#ifdef ROT_EXP_TIMING            /* (tools/build_exp_rot.sh, tools/pmc_shape.py: see above) */
 		n_iter++;
 #endif
 
@@ -342,7 +338,7 @@ rotwin_demod(const DemodLaunch &L)
 			else win.fir(ctab_addr, a, bank, C, __builtin_amdgcn_readfirstlane(rot), y.re, y.im);
 			if (PRIO) __builtin_amdgcn_s_setprio(ROT_PRIO_LEVEL);
 			ROT_TICK(2);
-#ifdef ROT_EXP_TIMING
+#ifdef ROT_EXP_TIMING            /* (tools/build_exp_rot.sh, tools/pmc_shape.py: see above) */
 			n_fir++;
 #endif
 
@@ -388,10 +384,7 @@ rotwin_demod(const DemodLaunch &L)
 			 * update, next to the Costas update, the AGC's square root and the quantiser, which need nothing from it */
 			rot_clock_fast<KS>(K, OQPSK ? (float)dual_state * MD_PI_F : MD_TWO_PI_F, v_end, t_phase, t_freq, isub, v_cur, fire_sub, fired,
 			                   OQPSK ? (ROT_OQ_SYNC ? 2 - slot : -1) : 0);
-#ifdef ROT_PRIO_SPLIT                /* experiment: what follows is off the path to the next FIR */
-			if (PRIO) __builtin_amdgcn_s_setprio(ROT_PRIO_SPLIT);
-#endif
-#ifdef ROT_EXP_TIMING
+#ifdef ROT_EXP_TIMING            /* (tools/build_exp_rot.sh, tools/pmc_shape.py: see above) */
 			if (!fired) n_slide++;                     /* (experiment: lanes the fast clock left to the stepping loop) */
 			if (md_any(!fired)) n_wslow++;
 #endif
@@ -443,7 +436,7 @@ rotwin_demod(const DemodLaunch &L)
 		}
 		if (OQPSK && ROT_OQ_SYNC) slot = __builtin_amdgcn_readfirstlane(3 - slot);      /* (keeps it in an SGPR: scalar branches) */
 	} while (--guard);
-#ifdef ROT_EXP_TIMING
+#ifdef ROT_EXP_TIMING            /* (tools/build_exp_rot.sh, tools/pmc_shape.py: see above) */
 	for (int o = 32; o > 0; o >>= 1) n_slide += __shfl_xor(n_slide, o);
 	if (blockIdx.x == 100 && threadIdx.x == 0)
 		printf("ROT_TIMING iters %u firs %u (lanes left to the stepping loop: %u of the wave's, in %u firings) cycles: clock %llu slide %llu fir %llu scalar %llu latch %llu\n", n_iter, n_fir, n_slide, n_wslow,

@@ -31,10 +31,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "demod_internal.h"
+#include "hip_host.h"
+#include "iq_load.h"
 #include "survey_detect.h"
 
 #define SV_BLOCK 256              /* sv_reduce */
@@ -55,21 +58,6 @@ struct SvArgs {
 	uint64_t      nseg;
 	uint32_t      n_rows, P;      /* parts per row: a multiple of the segments in flight per block */
 };
-
-template <int FMT>
-__device__ __forceinline__ float2
-sv_load(const void *iq, uint64_t i)
-{
-	if (FMT == 8) {
-		const uchar2 v = static_cast<const uchar2 *>(iq)[i];
-		return make_float2(static_cast<float>(static_cast<int>(v.x) - 128), static_cast<float>(static_cast<int>(v.y) - 128));
-	} else if (FMT == 16) {
-		const short2 v = static_cast<const short2 *>(iq)[i];
-		return make_float2(static_cast<float>(v.x), static_cast<float>(v.y));
-	} else {
-		return static_cast<const float2 *>(iq)[i];
-	}
-}
 
 /* where entry k of the twiddle table lives in LDS: one float2 of padding per 32, so that the passes' gathers at strides 4, 16, 64 ...
  * (and their doubles and triples) spread over the banks */
@@ -156,10 +144,10 @@ sv_spectrum(SvArgs A)
 			float2 a0 = make_float2(0.0f, 0.0f), a1 = a0, a2 = a0, a3 = a0;
 			if (active) {
 				const uint64_t at = seg * N + i;
-				a0 = sv_load<FMT>(A.iq, at);
-				a1 = sv_load<FMT>(A.iq, at + Q0);
-				a2 = sv_load<FMT>(A.iq, at + 2 * Q0);
-				a3 = sv_load<FMT>(A.iq, at + 3 * Q0);
+				a0 = md_load_iq<FMT>(A.iq, at);
+				a1 = md_load_iq<FMT>(A.iq, at + Q0);
+				a2 = md_load_iq<FMT>(A.iq, at + 2 * Q0);
+				a3 = md_load_iq<FMT>(A.iq, at + 3 * Q0);
 			}
 			/* cos(2 pi (i + q N / 4) / N) = c, -s, -c, s with (c, -s) = w1 */
 			const float h0 = __builtin_fmaf(-0.5f, w1.x, 0.5f), h1 = __builtin_fmaf(-0.5f, w1.y, 0.5f);
@@ -249,29 +237,7 @@ sv_fill_starts(uint64_t *starts, uint64_t pitch, uint64_t skip, uint32_t n)
 
 namespace {
 
-#define SV_TRY(expr)                                                                                 \
-	do {                                                                                             \
-		hipError_t e_ = (expr);                                                                      \
-		if (e_ != hipSuccess) {                                                                      \
-			mdm_note_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-			(void)hipGetLastError();                                                                 \
-			return e_ == hipErrorOutOfMemory ? MDEMOD_ERR_NOMEM : MDEMOD_ERR_HIP;                    \
-		}                                                                                            \
-	} while (0)
 #define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
-/* device memory that lives for one call */
-struct Scratch {
-	std::vector<void *> p;
-	~Scratch() { for (void *q : p) (void)hipFree(q); }
-	template <typename T> int get(T **out, size_t count) {
-		void *q = nullptr;
-		SV_TRY(hipMalloc(&q, count * sizeof(T) + 64));
-		p.push_back(q);
-		*out = static_cast<T *>(q);
-		return MDEMOD_OK;
-	}
-};
 
 struct SvGeometry {
 	int      log2n;
@@ -315,9 +281,7 @@ sv_launch_fmt(int log2n, dim3 grid, size_t lds, hipStream_t st, const SvArgs &A)
 	case 14: k = sv_spectrum<FMT, 14>; break;
 	default: REFUSE("survey: no spectrum kernel for 2^%d points", log2n);
 	}
-	SV_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-	hipLaunchKernelGGL(k, grid, dim3(sv_threads(log2n)), lds, st, A);
-	SV_TRY(hipGetLastError());
+	HIP_TRY(mdm_launch(k, grid, dim3(sv_threads(log2n)), lds, st, A));
 	return MDEMOD_OK;
 }
 
@@ -326,19 +290,19 @@ sv_spectrum_run(int bps, const void *iq_dev, uint64_t n_samples, uint32_t N, uin
 {
 	SvGeometry g;
 	sv_geometry(n_samples, N, n_rows, g);
-	Scratch mem;
+	MdmDevMem mem;
 	float2 *d_tw = nullptr;
 	float *d_part = nullptr;
-	int rc = mem.get(&d_tw, N / 8 + 1);
+	int rc = mem.alloc(&d_tw, N / 8 + 1);
 	if (rc) return rc;
-	rc = mem.get(&d_part, static_cast<size_t>(n_rows) * g.P * N);
+	rc = mem.alloc(&d_part, static_cast<size_t>(n_rows) * g.P * N);
 	if (rc) return rc;
 	std::vector<float2> tw(N / 8 + 1);
 	for (uint32_t k = 0; k <= N / 8; k++) {
 		const double a = 6.283185307179586476925 * k / N;
 		tw[k] = make_float2(static_cast<float>(cos(a)), static_cast<float>(-sin(a)));
 	}
-	SV_TRY(hipMemcpyAsync(d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, st));
 	SvArgs A;
 	A.iq = iq_dev; A.tw = d_tw; A.partial = d_part; A.per = g.per; A.nseg = g.nseg; A.n_rows = n_rows; A.P = g.P;
 	const dim3 grid(n_rows * (g.P / g.S));
@@ -348,8 +312,8 @@ sv_spectrum_run(int bps, const void *iq_dev, uint64_t n_samples, uint32_t N, uin
 	const uint64_t cells = static_cast<uint64_t>(n_rows) * N;
 	hipLaunchKernelGGL(sv_reduce, dim3(static_cast<uint32_t>((cells + SV_BLOCK - 1) / SV_BLOCK)), dim3(SV_BLOCK), 0, st, d_part, psd_dev, N, g.P,
 	                   g.per, g.nseg, n_rows);
-	SV_TRY(hipGetLastError());
-	SV_TRY(hipStreamSynchronize(st));                                   /* (the scratch memory goes with this call) */
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(st));                                   /* (the scratch memory goes with this call) */
 	return MDEMOD_OK;
 }
 
@@ -363,15 +327,6 @@ sv_check_spectrum_args(const mdemod_params *params, const void *iq, uint64_t n_s
 	if (n_samples / N < n_rows)
 		REFUSE("survey: %llu samples are %llu segments of fft_size %u, fewer than n_rows %u", static_cast<unsigned long long>(n_samples),
 		       static_cast<unsigned long long>(n_samples / N), N, n_rows);
-	return MDEMOD_OK;
-}
-
-int
-sv_select(int device)
-{
-	(void)hipGetLastError();
-	hipError_t e = hipSetDevice(device);
-	if (e != hipSuccess) { mdm_note_error("no usable HIP device %d: %s", device, hipGetErrorString(e)); (void)hipGetLastError(); return MDEMOD_ERR_HIP; }
 	return MDEMOD_OK;
 }
 
@@ -406,23 +361,23 @@ sv_confirm(const mdemod_params &params, const SurveySettings &s, std::vector<mde
 	mdemod_fe *fe = nullptr;
 	int rc = mdemod_fe_create(&in, &fp, &fe);
 	if (rc) return rc;
-	struct Guard { mdemod_fe *f; ~Guard() { mdemod_fe_destroy(f); } } guard{fe};
+	const std::unique_ptr<mdemod_fe, decltype(&mdemod_fe_destroy)> owner(fe, mdemod_fe_destroy);
 
-	Scratch mem;
+	MdmDevMem mem;
 	uint64_t *d_off = nullptr, *d_starts = nullptr;
 	uint32_t *d_cnt = nullptr, *d_nout = nullptr;
 	float *d_bb = nullptr, *d_est = nullptr;
-	if ((rc = mem.get(&d_off, K)) || (rc = mem.get(&d_starts, K)) || (rc = mem.get(&d_cnt, K)) || (rc = mem.get(&d_nout, K)) ||
-	    (rc = mem.get(&d_bb, 2 * n_bb * K)) || (rc = mem.get(&d_est, 4 * static_cast<size_t>(K))))
+	if ((rc = mem.alloc(&d_off, K)) || (rc = mem.alloc(&d_starts, K)) || (rc = mem.alloc(&d_cnt, K)) || (rc = mem.alloc(&d_nout, K)) ||
+	    (rc = mem.alloc(&d_bb, 2 * n_bb * K)) || (rc = mem.alloc(&d_est, 4 * static_cast<size_t>(K))))
 		return rc;
 	const std::vector<uint32_t> cnt(K, static_cast<uint32_t>(win_in));
-	SV_TRY(hipMemcpyAsync(d_off, starts.data(), K * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-	SV_TRY(hipMemcpyAsync(d_cnt, cnt.data(), K * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-	SV_TRY(hipStreamSynchronize(st));
+	HIP_TRY(hipMemcpyAsync(d_off, starts.data(), K * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_cnt, cnt.data(), K * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipStreamSynchronize(st));
 	rc = mdemod_fe_baseband_device(fe, iq_dev, d_off, d_cnt, d_bb, n_bb, static_cast<uint32_t>(n_bb), d_nout, st);
 	if (rc) return rc;
 	hipLaunchKernelGGL(sv_fill_starts, dim3((K + 63) / 64), dim3(64), 0, st, d_starts, n_bb, skip, K);
-	SV_TRY(hipGetLastError());
+	HIP_TRY(hipGetLastError());
 	mdemod_params bb = params;
 	bb.samplerate = params.samplerate / s.decimation;
 	bb.bps = 32;
@@ -432,8 +387,8 @@ sv_confirm(const mdemod_params &params, const SurveySettings &s, std::vector<mde
 	rc = mdemod_estimate_clock(&bb, d_bb, n_bb * K, d_starts, d_freq, nullptr, K, window, d_tf, d_kq, st);
 	if (rc) return rc;
 	std::vector<float> est(4 * static_cast<size_t>(K));
-	SV_TRY(hipMemcpyAsync(est.data(), d_est, est.size() * sizeof(float), hipMemcpyDeviceToHost, st));
-	SV_TRY(hipStreamSynchronize(st));
+	HIP_TRY(hipMemcpyAsync(est.data(), d_est, est.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
 	const double hz_per_rad = params.symrate * (params.oqpsk ? 2.0 : 1.0) / (2 * 3.141592653589793);
 	for (uint32_t k = 0; k < K; k++) {
 		mdemod_survey_hit &h = hits[k];
@@ -467,7 +422,7 @@ mdemod_spectrum_device(const mdemod_params *params, const void *iq_dev, uint64_t
 try { MDEMOD_API_ENTER
 	int rc = sv_check_spectrum_args(params, iq_dev, n_samples, fft_size, n_rows, psd_dev);
 	if (rc) return rc;
-	rc = sv_select(params->device);
+	rc = mdm_select_device(params->device);
 	if (rc) return rc;
 	return sv_spectrum_run(params->bps, iq_dev, n_samples, fft_size, n_rows, psd_dev, static_cast<hipStream_t>(hip_stream));
 } MDEMOD_API_CATCH
@@ -489,18 +444,18 @@ try { MDEMOD_API_ENTER
 	const uint64_t nseg = n_samples / N;
 	if (nseg == 0) REFUSE("survey: %llu samples are less than one segment of fft_size %u", static_cast<unsigned long long>(n_samples), N);
 	const uint32_t rows = static_cast<uint32_t>(std::min<uint64_t>(s.n_rows, nseg));
-	rc = sv_select(params->device);
+	rc = mdm_select_device(params->device);
 	if (rc) return rc;
 	hipStream_t st = static_cast<hipStream_t>(hip_stream);
-	Scratch mem;
+	MdmDevMem mem;
 	float *d_psd = nullptr;
-	rc = mem.get(&d_psd, static_cast<size_t>(rows) * N);
+	rc = mem.alloc(&d_psd, static_cast<size_t>(rows) * N);
 	if (rc) return rc;
 	rc = sv_spectrum_run(params->bps, iq_dev, n_samples, N, rows, d_psd, st);
 	if (rc) return rc;
 	std::vector<float> psd(static_cast<size_t>(rows) * N);
-	SV_TRY(hipMemcpyAsync(psd.data(), d_psd, psd.size() * sizeof(float), hipMemcpyDeviceToHost, st));
-	SV_TRY(hipStreamSynchronize(st));
+	HIP_TRY(hipMemcpyAsync(psd.data(), d_psd, psd.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
 	std::vector<mdemod_survey_hit> found;
 	rc = mdemod_survey_detect_host(*params, s, psd.data(), N, rows, found);
 	if (rc) return rc;
@@ -529,7 +484,7 @@ try { MDEMOD_API_ENTER
 	if (rc) return rc;
 	const uint32_t N = s.fft_size;
 	if (n_samples / N == 0) REFUSE("survey: %llu samples are less than one segment of fft_size %u", static_cast<unsigned long long>(n_samples), N);
-	rc = sv_select(params->device);
+	rc = mdm_select_device(params->device);
 	if (rc) return rc;
 	hipStream_t st = nullptr;
 	const size_t sb = 2 * static_cast<size_t>(params->bps) / 8;
@@ -540,24 +495,24 @@ try { MDEMOD_API_ENTER
 	std::vector<float> psd;
 	std::vector<uint64_t> row_start;
 	{
-		Scratch mem;
+		MdmDevMem mem;
 		unsigned char *d_in = nullptr;
 		float *d_psd = nullptr;
-		rc = mem.get(&d_in, static_cast<size_t>(std::min(piece, usable)) * sb);
+		rc = mem.alloc(&d_in, static_cast<size_t>(std::min(piece, usable)) * sb);
 		if (rc) return rc;
-		rc = mem.get(&d_psd, static_cast<size_t>(s.n_rows) * N);
+		rc = mem.alloc(&d_psd, static_cast<size_t>(s.n_rows) * N);
 		if (rc) return rc;
 		for (uint64_t at = 0; at < usable; at += piece) {
 			const uint64_t len = std::min(piece, usable - at), segs = len / N;
 			uint64_t rows = std::max<uint64_t>(1, static_cast<uint64_t>(static_cast<double>(s.n_rows) * len / usable));
 			rows = std::min<uint64_t>(std::min<uint64_t>(rows, segs), s.n_rows);
 			if (row_start.size() + rows > MDEMOD_SURVEY_MAX_ROWS) rows = 1;
-			SV_TRY(hipMemcpy(d_in, src + at * sb, len * sb, hipMemcpyHostToDevice));
+			HIP_TRY(hipMemcpy(d_in, src + at * sb, len * sb, hipMemcpyHostToDevice));
 			rc = sv_spectrum_run(params->bps, d_in, len, N, static_cast<uint32_t>(rows), d_psd, st);
 			if (rc) return rc;
 			const size_t have = psd.size();
 			psd.resize(have + rows * N);
-			SV_TRY(hipMemcpy(psd.data() + have, d_psd, rows * N * sizeof(float), hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(psd.data() + have, d_psd, rows * N * sizeof(float), hipMemcpyDeviceToHost));
 			for (uint64_t r = 0; r < rows; r++) row_start.push_back(at + r * (segs / rows) * N);
 		}
 	}
@@ -568,14 +523,14 @@ try { MDEMOD_API_ENTER
 	if (!found.empty()) {
 		/* the candidates' windows side by side in device memory */
 		const uint64_t win_in = sv_window_in(s, n_samples);
-		Scratch mem;
+		MdmDevMem mem;
 		unsigned char *d_win = nullptr;
-		rc = mem.get(&d_win, static_cast<size_t>(win_in) * sb * found.size());
+		rc = mem.alloc(&d_win, static_cast<size_t>(win_in) * sb * found.size());
 		if (rc) return rc;
 		std::vector<uint64_t> starts(found.size());
 		for (size_t k = 0; k < found.size(); k++) {
 			const uint64_t from = std::min<uint64_t>(row_start[found[k].best_row], n_samples - win_in);
-			SV_TRY(hipMemcpy(d_win + k * win_in * sb, src + from * sb, win_in * sb, hipMemcpyHostToDevice));
+			HIP_TRY(hipMemcpy(d_win + k * win_in * sb, src + from * sb, win_in * sb, hipMemcpyHostToDevice));
 			starts[k] = k * win_in;
 		}
 		rc = sv_confirm(*params, s, found, d_win, starts, win_in, st);
