@@ -28,6 +28,7 @@ struct mdemod_ctx {
 	DemodStateSoA st;
 	float        *d_ctab;
 	float        *d_lut;
+	int32_t      *d_clock_tab; /* the symbol clock's position table (tab.clock_tab), NULL without one */
 	float        *d_rrc;       /* plain polyphase table [bank][taps] (filter.c:18-22) for the latency kernel */
 	int           hyb_block;   /* hybrid window (tab.rw_hyb): threads per block */
 	bool          v1_global_table;   /* v1 ring kernel with its coefficient table left in global memory (it does not fit the LDS) */
@@ -84,6 +85,7 @@ launch(mdemod_ctx *ctx, DemodLaunch &L, hipStream_t stream)
 	L.ctab = ctx->d_ctab;
 	L.ctab_floats = static_cast<uint32_t>(ctx->tab.ctab.size());
 	L.tanh_lut = ctx->d_lut;
+	L.c.clock_tab = ctx->d_clock_tab;
 	/* Few streams: one stream per WAVE (demod_kernel_lat.hip) instead of one per lane.  A lane runs ~0.8 M symbols/s whatever
 	 * the batch, a wave 1.5 times that, and below a few thousand streams most of the GPU idles either way. */
 	if (wants_latency_kernel(ctx)) {
@@ -115,6 +117,7 @@ upload_tables(mdemod_ctx *ctx)
 	HIP_TRY(hipMemcpyAsync(ctx->d_ctab, ctx->tab.ctab.data(), ctx->tab.ctab.size() * sizeof(float), hipMemcpyHostToDevice, own.s));
 	HIP_TRY(hipMemcpyAsync(ctx->d_rrc, ctx->tab.rrc.data(), ctx->tab.rrc.size() * sizeof(float), hipMemcpyHostToDevice, own.s));
 	HIP_TRY(hipMemcpyAsync(ctx->d_lut, ctx->tab.tanh_lut, sizeof(ctx->tab.tanh_lut), hipMemcpyHostToDevice, own.s));
+	if (ctx->d_clock_tab) HIP_TRY(hipMemcpyAsync(ctx->d_clock_tab, ctx->tab.clock_tab.data(), ctx->tab.clock_tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, own.s));
 	const int rc = mdemod_reset(ctx, own.s);
 	if (rc) return rc;
 	HIP_TRY(hipStreamSynchronize(own.s));
@@ -185,14 +188,26 @@ plan_context(mdemod_ctx *ctx)
 	c.sin_lut = ((ctx->use_rot && !ctx->tab.rw_std_compact && c.step_safe == (c.oqpsk ? 6 : 14)) ||
 	             (ctx->tab.rw_compact4 && ctx->tab.rw_wide && params->bps == 16 && !c.oqpsk && c.step_safe == 109)) ? 1 : 0;
 	auto rw_block = [&]() { return ctx->tab.rw_wide ? MDEMOD_RW_WIDE_BLOCK : (c.sin_lut ? MDEMOD_RW_LUT_BLOCK : MDEMOD_RW_BLOCK); };
+	/* The symbol clock's position table (rotwin_body.h: rot_clock_fast, 64 bytes per bank behind everything else in LDS) for every
+	 * rotating-window context whose clock takes a fixed number of blind steps: the std window's instances with 14 / 6 compiled-in
+	 * steps (they never look at a jump schedule) and the generic bodies without a schedule (clock_jump.h) - not the instance with
+	 * 109 compiled-in steps (closed form).  The table is the first thing to go when the LDS is short. */
+	auto want_clock_tab = [&]() {
+		if (!ctx->tab.use_rw || c.interp > 64) return false;
+		if (c.sin_lut) return ctx->use_rot;
+		return c.jump[0].nb == 0 && c.jump[1].nb == 0;
+	};
+	bool clock_tab = want_clock_tab();
 	auto lds_need = [&](int threads) {
 		return (ctx->tab.ctab.size() + 32) * sizeof(float) +
 		       (ctx->tab.use_rw ? static_cast<size_t>(rw_block() / 64) * MDEMOD_RW_STATE_SLOTS * 64 * sizeof(float)
 		                          + static_cast<size_t>(rw_block()) * 64     /* soft-symbol staging: a 32-symbol ring (4 x 16 B) per thread */
 		                          + (c.sin_lut ? static_cast<size_t>(MDEMOD_SIN_LUT_BYTES) : 0)
+		                          + (clock_tab ? static_cast<size_t>(c.interp) * 4 * 16 : 0)
 		                        : static_cast<size_t>(threads / 64) * c.ring_granules * 64 * 4 * ctx->sample_bytes);
 	};
-	if (c.sin_lut && lds_need(ctx->block_threads) > 160 * 1024) c.sin_lut = 0;      /* (e.g. -O 7 at a rate that has 14 blind steps: 38 KB of rows) */
+	if (c.sin_lut && lds_need(ctx->block_threads) > 160 * 1024) { c.sin_lut = 0; clock_tab = want_clock_tab(); }      /* (e.g. -O 7 at a rate that has 14 blind steps: 38 KB of rows) */
+	if (clock_tab && lds_need(ctx->block_threads) > 160 * 1024) clock_tab = false;
 	if (ctx->tab.use_rw && lds_need(ctx->block_threads) > 160 * 1024) {
 		/* The per-alignment coefficient rows of the std geometry grow with -O (16 alignments x interp x 84 floats: past the
 		 * 160 KB of LDS from -O 29 on); the v1 ring kernel keeps 4 alignments and still fits: fall back to it. */
@@ -201,9 +216,15 @@ plan_context(mdemod_ctx *ctx)
 		if (rc) return rc;
 		c.ring_granules = c.hpad / 4 + 8;
 		c.sin_lut = 0;
+		clock_tab = false;
 	}
 	while (ctx->block_threads > 64 && lds_need(ctx->block_threads) > 160 * 1024) ctx->block_threads -= 64;
 	ctx->lds_bytes = lds_need(ctx->block_threads);
+	ctx->tab.clock_tab.clear();
+	if (clock_tab) {
+		ctx->tab.clock_tab.resize(static_cast<size_t>(c.interp) * 16);
+		if (mdemod_clock_table(c.interp, c.step_safe, ctx->tab.clock_tab.data(), static_cast<uint32_t>(4 * c.interp)) != 4 * c.interp) return MDEMOD_ERR_PARAM;
+	}
 	ctx->v1_global_table = false;
 	if (ctx->lds_bytes > 160 * 1024) {
 		/* not even one wave's ring fits next to the table (-O 64 with 129 taps, ...): the v1 kernel reads its coefficients from
@@ -318,6 +339,7 @@ mdemod_create(const mdemod_params *params, mdemod_ctx **out)
 	CREATE_TRY(ctx->mem.alloc(&s.events, n * MDEMOD_MAX_LOCK_EVENTS));
 	CREATE_TRY(ctx->mem.alloc(&ctx->d_ctab, ctx->tab.ctab.size()));
 	CREATE_TRY(ctx->mem.alloc(&ctx->d_lut, 32));
+	if (!ctx->tab.clock_tab.empty()) CREATE_TRY(ctx->mem.alloc(&ctx->d_clock_tab, ctx->tab.clock_tab.size()));
 	CREATE_TRY(ctx->mem.alloc(&ctx->d_rrc, ctx->tab.rrc.size()));
 	/* tables and the power-on state go in on a stream of their own, and only that stream is waited for: a context made while
 	   other contexts run (a second host thread, a recording's tile bank next to its serial head) must not wait for their
@@ -770,6 +792,27 @@ try { MDEMOD_API_ENTER
 		snprintf(name, name_cap, "%s%s", mdemod_kernel_name(ctx), ctx->v1_global_table && !wants_latency_kernel(ctx) ? " [table in global memory]" : "");
 		if (lds_bytes) *lds_bytes = static_cast<uint32_t>(wants_latency_kernel(ctx) ? ctx->lat_lds : ctx->lds_bytes);
 		if (block_threads) *block_threads = static_cast<uint32_t>(ctx->tab.use_rw ? (ctx->tab.rw_wide ? MDEMOD_RW_WIDE_BLOCK : (ctx->tab.c.sin_lut ? MDEMOD_RW_LUT_BLOCK : MDEMOD_RW_BLOCK)) : ctx->block_threads);
+	}
+	delete ctx;
+	return rc;
+} MDEMOD_API_CATCH
+
+int
+mdemod_plan_clock_table(const mdemod_params *params, int32_t *out, uint32_t cap_entries)
+try { MDEMOD_API_ENTER
+	if (!params || params->n_streams == 0) return MDEMOD_ERR_PARAM;
+	mdemod_ctx *ctx = new (std::nothrow) mdemod_ctx();
+	if (!ctx) return MDEMOD_ERR_NOMEM;
+	ctx->params = *params;
+	ctx->pipe = nullptr;
+	int rc = plan_context(ctx);
+	if (rc == MDEMOD_OK) {
+		const size_t entries = ctx->tab.clock_tab.size() / 4;
+		if (out && entries > cap_entries) rc = MDEMOD_ERR_PARAM;
+		else {
+			if (out && entries) memcpy(out, ctx->tab.clock_tab.data(), ctx->tab.clock_tab.size() * sizeof(int32_t));
+			rc = static_cast<int>(entries);
+		}
 	}
 	delete ctx;
 	return rc;

@@ -88,6 +88,31 @@ mdemod_last_error(void)
 	return tl_error;
 }
 
+extern "C" uint32_t
+mdemod_clock_interp_magic(int32_t interp)
+{
+	if (interp < 1) return 0;
+	return static_cast<uint32_t>((1ull << 32) / static_cast<uint64_t>(interp)) + 1u;
+}
+
+extern "C" int
+mdemod_clock_table(int32_t interp, int32_t k_safe, int32_t *out, uint32_t cap_entries)
+{
+	if (interp < 1 || interp > 64 || k_safe < 0 || !out) return 0;
+	if (cap_entries < 4u * static_cast<uint32_t>(interp)) return MDEMOD_ERR_PARAM;
+	for (int32_t isub = 0; isub < interp; isub++)
+		for (int32_t j = 0; j < 4; j++) {
+			const int32_t w = isub + k_safe + 1 + j, q = w / interp, isub_new = w - q * interp;
+			const int32_t fire_sub = isub_new ? isub_new - 1 : interp - 1;
+			int32_t *e = out + 4 * (isub * 4 + j);
+			e[0] = q + (isub_new > 0 ? 1 : 0) - (isub > 0 ? 1 : 0);
+			e[1] = fire_sub;
+			e[2] = isub_new;
+			e[3] = interp - 1 - fire_sub;
+		}
+	return 4 * interp;
+}
+
 int
 mdemod_host_derive(const mdemod_params &p, HostTables &out, int generation)
 {
@@ -111,6 +136,8 @@ mdemod_host_derive(const mdemod_params &p, HostTables &out, int generation)
 	c.taps = 2 * p.rrc_order + 1;
 	c.oqpsk = p.oqpsk ? 1 : 0;
 	c.sin_lut = 0;                                    /* (decided by plan_context once the kernel instance and its LDS are known) */
+	c.clock_tab = nullptr;                            /* (device pointer: set at launch) */
+	out.clock_tab.clear();                            /* (plan_context, like sin_lut) */
 
 	/* demod.c:10-14 */
 	const int mult = p.oqpsk ? 1 : 2;
@@ -164,7 +191,7 @@ mdemod_host_derive(const mdemod_params &p, HostTables &out, int generation)
 		int ks = static_cast<int>(floor((thr_min - f_hi - 0.05 - 1e-3) / f_hi));
 		c.step_safe = ks < 0 ? 0 : ks;
 		c.step_check = 4;                                         /* fixed in the kernel */
-		c.interp_magic = static_cast<uint32_t>((1ull << 32) / static_cast<uint64_t>(c.interp)) + 1u;
+		c.interp_magic = mdemod_clock_interp_magic(c.interp);
 		c.step_inv = static_cast<float>((1.0 - 1.0 / 4096.0) / static_cast<double>(c.step_fmax));
 		/* long runs (a high sample rate times -O): most of the steps in closed form, binade by binade (clock_jump.h; the v3 body only) */
 		const double pi_f = static_cast<double>(static_cast<float>(kPi)), two_pi_f = 2.0 * pi_f;

@@ -16,6 +16,7 @@ struct HostTables {
 	std::vector<float> rrc;       /* interp*taps, bank-major (filter.c:20)     */
 	std::vector<float> ctab;      /* [4 alignments][interp banks][row stride]  */
 	float              tanh_lut[32];
+	std::vector<int32_t> clock_tab; /* the symbol clock's position table (mdemod_clock_table), 16 words per bank; empty: the kernel keeps the arithmetic (filled by plan_context) */
 	bool               rw_wide;   /* wide geometry (160-slot packed window, compact table, 512-thread blocks): <= 129 taps at <= 15 samples per firing, on v3 also 66..129 taps at 15..30 (wide_far_ok) */
 	bool               rw_far;    /* far geometry: <= 65 taps at 15..46 samples per firing (112-slot packed window, 47 alignments; far_ok); with rw_hyb: the 120-slot hybrid window, float input at 30..54 (hyb_far_ok) */
 	bool               rw_mid;    /* mid geometry: <= 65 taps at 3.6..15 samples per firing (96-slot packed window, compact table); with rw_hyb: the 96-slot hybrid window, float input, <= 65 taps at <= 30 */

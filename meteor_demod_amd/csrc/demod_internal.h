@@ -48,6 +48,7 @@ struct DemodConsts {
 	float    step_inv;       /* (1 - 2^-12) / step_fmax: steps that fit a phase distance, strictly conservative (clock_jump.h) */
 	int32_t  sin_lut;        /* host only: this context launches the kernel instance with the sine table in LDS */
 	cj_sched jump[2];        /* the symbol clock's runs in closed form (clock_jump.h): [0] from 0, [1] the second rail of an OQPSK symbol; nb == 0: not used */
+	const int32_t *clock_tab; /* device: the symbol clock's position table, 4 * interp entries of 4 words (mdemod_clock_table; set at launch); NULL: this context keeps the arithmetic */
 };
 
 /* Per-stream state, structure-of-arrays in HBM so that lane s of a wave touches

@@ -101,6 +101,22 @@ int  mdemod_derive_tables(const mdemod_params *params, float *rrc_out, uint32_t 
  * v1 kernel that leaves its table in global memory is marked), the dynamic LDS bytes and the threads per block. */
 int  mdemod_plan_kernel(const mdemod_params *params, char *name, uint32_t name_cap, uint32_t *lds_bytes, uint32_t *block_threads);
 
+/* The symbol clock's position table of the rotating-window kernels (rotwin_body.h: rot_clock_fast) - host only.  A firing's clock
+ * takes k_safe blind steps and up to four checked ones; with k_safe fixed, where the next firing lies depends only on isub (the
+ * interpolation phase, 0..interp-1) and j (how many of the first three checked steps stayed below the threshold, 0..3).  Entry
+ * isub * 4 + j is four words { dv, fire_sub, isub_new, bank }: with w = isub + k_safe + 1 + j and q = w / interp,
+ * isub_new = w - q * interp, dv = q + (isub_new > 0) - (isub > 0) input samples to advance, fire_sub = isub_new ? isub_new - 1
+ * : interp - 1 (filter.c:52's interp_idx of the firing) and bank = interp - 1 - fire_sub.  Returns the number of entries written
+ * (4 * interp), 0 when there is no table (interp outside 1..64: more than 4 KB of LDS), < 0 when `cap` (in entries) is too small. */
+/* DemodConsts::interp_magic, floor(2^32 / interp) + 1: w / interp == mulhi(w, magic) for the small w of the symbol clock (interp >= 2;
+ * the magic of 1 does not fit 32 bits and the kernels do not use it).  What the contexts that keep the arithmetic divide with. */
+uint32_t mdemod_clock_interp_magic(int32_t interp);
+int  mdemod_clock_table(int32_t interp, int32_t k_safe, int32_t *out, uint32_t cap_entries);
+/* The table mdemod_create would hand the kernel of `params` (out may be NULL: only the count): 0 entries for a context that keeps the
+ * arithmetic - a symbol clock with a jump schedule (clock_jump.h) or the instance with 109 compiled-in steps, a kernel that is not
+ * one of the rotating-window ones, or a table that does not fit the LDS next to the rest. */
+int  mdemod_plan_clock_table(const mdemod_params *params, int32_t *out, uint32_t cap_entries);
+
 /* RRC polyphase table as filter_init_rrc lays it out (filter.c:18-22):
  * interp*taps floats, bank-major.  Returns number of floats, or <0. */
 int  mdemod_get_rrc_table(const mdemod_ctx *ctx, float *out, uint32_t cap);

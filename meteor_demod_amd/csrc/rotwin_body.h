@@ -87,10 +87,17 @@ blind_steps(float p, float f)
  * threshold, then four checked ones (the increment is positive, so "reached" is monotone); every add is the reference's add
  * (k * freq != k rounded adds).  Does nothing when the lane is too close to the threshold or to the end of its block: the
  * caller's generic loop steps those. */
-struct RotClockConsts { int k_safe, steps_need, interp; float f_hi; uint32_t magic; float inv; const cj_sched *jump; };   /* jump: the launch arguments' two schedules, read where they are used (scalar loads) rather than held in registers */
+/* The position of the next firing from a table (demod_host.cpp: mdemod_clock_table).  With a fixed number of blind steps everything
+ * behind the four checked steps depends on two small integers: isub (< -O) and j, the number of the first three checked steps that
+ * stayed below the threshold.  One 16-byte LDS read at isub * 4 + j replaces the division by -O, the two carries and the bank
+ * arithmetic (24 VALU instructions of a firing, with an LDS pipe that is idle: profiles/r07_clock_table.md).
+ * An entry is { samples to advance, fire_sub (filter.c:52's `interp_idx`, host tests only), isub, bank }. */
+typedef int rot_i4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(3))) rot_i4 *rot_clktab_t;
+struct RotClockConsts { int k_safe, steps_need, interp; float f_hi; uint32_t magic; float inv; const cj_sched *jump; rot_clktab_t tab; };   /* jump: the launch arguments' two schedules, read where they are used (scalar loads) rather than held in registers; tab: null = this context keeps the arithmetic */
 template <int KS>          /* KS > 0: the number of blind steps is known at compile time (the launcher checks it), 0: any */
 __device__ __forceinline__ void
-rot_clock_fast(const RotClockConsts &K, float thr, int v_end, float &t_phase, float t_freq, int &isub, int &v_cur, int &fire_sub, bool &fired, int jidx = -1)
+rot_clock_fast(const RotClockConsts &K, float thr, int v_end, float &t_phase, float t_freq, int &isub, int &v_cur, int &bank, bool &fired, int jidx = -1)
 {
 	int k_safe = KS ? KS : K.k_safe;
 	const int interp = K.interp;
@@ -118,17 +125,26 @@ rot_clock_fast(const RotClockConsts &K, float thr, int v_end, float &t_phase, fl
 		}
 		const float p1 = p + t_freq, p2 = p1 + t_freq, p3 = p2 + t_freq, p4 = p3 + t_freq;
 		const bool c1 = p1 >= thr, c2 = p2 >= thr, c3 = p3 >= thr, c4 = p4 >= thr;
-		const int m = k_safe + 1 + (c1 ? 0 : 1) + (c2 ? 0 : 1) + (c3 ? 0 : 1);
 		float ph = c3 ? p3 : p4;
 		ph = c2 ? p2 : ph;
 		ph = c1 ? p1 : ph;
 		t_phase = ph;
-		const uint32_t w = (uint32_t)(isub + m);
-		const uint32_t q = (interp == 1) ? w : __umulhi(w, K.magic);     /* floor(w / interp); the magic of 1 does not fit 32 bits */
-		const int isub_new = (int)(w - q * (uint32_t)interp);
-		v_cur += (int)q + (isub_new > 0 ? 1 : 0) - (isub > 0 ? 1 : 0);   /* samples pushed: ceil(w/interp) - (isub>0) */
-		fire_sub = (isub_new == 0) ? interp - 1 : isub_new - 1;
-		isub = isub_new;
+		/* the instances with compiled-in blind steps always have the table (the launcher checks it); the generic one asks (wave-uniform) */
+		if ((KS == 14 || KS == 6) || (KS == 0 && K.tab)) {
+			const uint32_t off = ((uint32_t)isub << 6) + (c1 ? 0u : 16u) + (c2 ? 0u : 16u) + (c3 ? 0u : 16u);      /* entry isub * 4 + j */
+			const rot_i4 e = *reinterpret_cast<rot_clktab_t>(reinterpret_cast<const __attribute__((address_space(3))) unsigned char *>(K.tab) + off);
+			v_cur += e.x;
+			isub = e.z;
+			bank = e.w;
+		} else {
+			const uint32_t w = (uint32_t)(isub + k_safe + 1 + (c1 ? 0 : 1) + (c2 ? 0 : 1) + (c3 ? 0 : 1));
+			const uint32_t q = (interp == 1) ? w : __umulhi(w, K.magic);     /* floor(w / interp); the magic of 1 does not fit 32 bits */
+			const int isub_new = (int)(w - q * (uint32_t)interp);
+			v_cur += (int)q + (isub_new > 0 ? 1 : 0) - (isub > 0 ? 1 : 0);   /* samples pushed: ceil(w/interp) - (isub>0) */
+			const int fire_sub = (isub_new == 0) ? interp - 1 : isub_new - 1;
+			bank = interp - 1 - fire_sub;                                    /* filter.c:52 */
+			isub = isub_new;
+		}
 		fired = c4;
 	}
 }
@@ -172,6 +188,8 @@ rotwin_demod(const DemodLaunch &L)
 	rot_sinlut_t *sintab = reinterpret_cast<rot_sinlut_t *>(stage - threadIdx.x + BLOCK * RGR);
 	if constexpr (LUT) md_sin_lut_fill(sintab, (int)threadIdx.x, BLOCK);
 	win.setup(ctab_addr + (uint32_t)(reinterpret_cast<unsigned char *>(stage - threadIdx.x + BLOCK * RGR) - lds) + (LUT ? MDEMOD_SIN_LUT_BYTES : 0));
+	/* the symbol clock's position table (rot_clock_fast): 4 entries of 16 bytes per -O, behind everything else */
+	rot_i4 *clktab = reinterpret_cast<rot_i4 *>(reinterpret_cast<unsigned char *>(stage - threadIdx.x + BLOCK * RGR) + (LUT ? MDEMOD_SIN_LUT_BYTES : 0));
 
 	const DemodConsts &C = L.c;
 	const uint32_t stream = blockIdx.x * blockDim.x + threadIdx.x;
@@ -179,6 +197,9 @@ rotwin_demod(const DemodLaunch &L)
 
 	for (uint32_t i = threadIdx.x; i < L.ctab_floats; i += blockDim.x) ctab[i] = L.ctab[i];
 	if (threadIdx.x < 32) lut[threadIdx.x] = L.tanh_lut[threadIdx.x];
+	const bool has_clktab = KS != 109 && C.clock_tab != nullptr;               /* (wave-uniform: a launch argument) */
+	if (has_clktab)
+		for (int i = (int)threadIdx.x; i < 4 * C.interp; i += (int)blockDim.x) clktab[i] = reinterpret_cast<const rot_i4 *>(C.clock_tab)[i];
 
 	int n = 0;
 	const sample_t *src = nullptr;
@@ -242,7 +263,7 @@ rotwin_demod(const DemodLaunch &L)
 		g_load += NST;
 	}
 
-	__syncthreads();                                       /* coefficient rows + LUT visible */
+	__syncthreads();                                       /* coefficient rows + LUTs + clock table visible */
 
 	int rot = 0;                                           /* physical chunk that is logical chunk 0 (wave-uniform) */
 	/* OQPSK: demod.c:62-84 does half the work on the I-rail firing (state 1: one mixer product, no timing or Costas update, no
@@ -251,15 +272,20 @@ rotwin_demod(const DemodLaunch &L)
 	 * `emit` branches below are scalar and the I-rail iterations skip that code instead of running it masked off. */
 	int slot = 1;
 	int base = 0;
-	int v_cur = kBack - 1;
-	int isub = 0, fire_sub = 0;
+	int isub = 0, bank = interp - 1;                       /* bank: filter.c:52's `interp - 1 - interp_idx` of the pending firing */
 	bool fired = false;
 	bool done = !valid || n == 0;
+	/* A lane that is done parks its sample position past everything: the loop's votes are then comparisons of v_cur alone, whose
+	 * masks the vote reads as they are (a vote on a bool that lives in a lane mask costs a v_cndmask 0/1 + v_cmp_ne each time:
+	 * two of them per iteration until round 7) */
+	constexpr int V_DONE = 0x3FFFFFFF;
+	int v_cur = done ? V_DONE : kBack - 1;
 	uint32_t sym_call = 0;
 	RotClockConsts K;
 	K.k_safe = C.step_safe; K.f_hi = C.step_fmax; K.magic = C.interp_magic; K.interp = C.interp; K.inv = C.step_inv;
 	K.steps_need = ((KS == 109 ? CJ109_MAX_STEPS : C.step_safe) + 4 + C.interp - 1) / C.interp;      /* samples that hold k_safe + 4 steps */
 	K.jump = C.jump;
+	K.tab = has_clktab ? (rot_clktab_t)clktab : (rot_clktab_t)0;
 
 	int n_wave_max = n;
 	for (int o = 32; o > 0; o >>= 1) {
@@ -283,30 +309,33 @@ rotwin_demod(const DemodLaunch &L)
 		 * lanes that ran ahead of the window.  A lane that fires does its next clock inside the firing (below). ---- */
 		if (!fired && !done) {
 			const float thr = OQPSK ? (float)dual_state * MD_PI_F : MD_TWO_PI_F;
-			rot_clock_fast<KS>(K, thr, v_end, t_phase, t_freq, isub, v_cur, fire_sub, fired);
+			rot_clock_fast<KS>(K, thr, v_end, t_phase, t_freq, isub, v_cur, bank, fired);
 			while (!fired && !done) {
 				if (isub == 0) {
-					if (v_cur + 1 >= v_end) { done = true; break; }
+					if (v_cur + 1 >= v_end) { done = true; v_cur = V_DONE; break; }
 					v_cur++;
 				}
 				t_phase = t_phase + t_freq;
-				fire_sub = isub;
+				bank = interp - 1 - isub;
 				isub = (isub + 1 == interp) ? 0 : isub + 1;
 				if (t_phase >= thr) fired = true;
 			}
 		}
-		if (md_all(done)) break;
+		/* everybody done: with a window the slide's vote below asks (a wave that is done passes it), and only then */
+		if constexpr (GATHER) if (md_all(v_cur == V_DONE)) break;
 		ROT_TICK(0);
 #ifdef ROT_EXP_TIMING            /* (tools/build_exp_rot.sh, tools/pmc_shape.py: see above) */
 		n_iter++;
 #endif
 
 		/* ---- (2) slide: when nobody needs logical chunk 0 any more it becomes the newest chunk ---- */
+		bool all_done = false;
 		if constexpr (!GATHER)
 #pragma unroll
 		for (int r = 0; r < W::MAXSL; r++) {
 			const int a_now = v_cur - kBack - base;
-			if (md_all(done || a_now >= SLIDE)) {
+			if (md_all(a_now >= SLIDE)) {                              /* (a lane that is done: V_DONE) */
+				if (md_all(v_cur == V_DONE)) { all_done = true; break; }
 				RGran<FMT> g[GPS];
 #pragma unroll
 				for (int i = 0; i < GPS; i++) g[i] = stg[i];
@@ -326,13 +355,13 @@ rotwin_demod(const DemodLaunch &L)
 				g_load += GPS;
 			}
 		}
+		if (all_done) break;
 
 		ROT_TICK(1);
 		/* ---- (3) the firing, if its taps are inside the window ---- */
 		const int a = v_cur - kBack - base;
 		if (fired && (GATHER || a <= AMAX) && (!(OQPSK && ROT_OQ_SYNC) || dual_state == slot)) {
 			fired = false;
-			const int bank = interp - 1 - fire_sub;                     /* filter.c:52 */
 			cf32 y;
 			if constexpr (GATHER) win.fir_gather(ctab_addr, src, hist_in, v_cur, n, bank, C, y.re, y.im);
 			else win.fir(ctab_addr, a, bank, C, __builtin_amdgcn_readfirstlane(rot), y.re, y.im);
@@ -382,7 +411,7 @@ rotwin_demod(const DemodLaunch &L)
 			}
 			/* the clock's way to the NEXT firing starts here: a chain of ~20 dependent adds that needs nothing but the timing
 			 * update, next to the Costas update, the AGC's square root and the quantiser, which need nothing from it */
-			rot_clock_fast<KS>(K, OQPSK ? (float)dual_state * MD_PI_F : MD_TWO_PI_F, v_end, t_phase, t_freq, isub, v_cur, fire_sub, fired,
+			rot_clock_fast<KS>(K, OQPSK ? (float)dual_state * MD_PI_F : MD_TWO_PI_F, v_end, t_phase, t_freq, isub, v_cur, bank, fired,
 			                   OQPSK ? (ROT_OQ_SYNC ? 2 - slot : -1) : 0);
 #ifdef ROT_EXP_TIMING            /* (tools/build_exp_rot.sh, tools/pmc_shape.py: see above) */
 			if (!fired) n_slide++;                     /* (experiment: lanes the fast clock left to the stepping loop) */
