@@ -31,6 +31,9 @@
  * confirmed by their symbol-rate line) and uses the first confirmed signal's offset - each file of a batch its own; no confirmed
  * signal is exit 1 before any output file exists.  --decimate auto takes the largest N the front end accepts; --scan prints the
  * candidates and exits.  Weak references as well.
+ * --cadu runs the frame layer (include/meteor_demod_amd_frames.h) over every output file once it is complete and closed: sync
+ * search and Viterbi decoding on the GPU, the CADUs (1024 bytes each) into <output without .s>.cadu, one line about them on stdout.
+ * Weak references again; refused with --stdout.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -49,6 +52,7 @@
 #include "meteor_demod_amd.h"
 #include "meteor_demod_amd_frontend.h"
 #include "meteor_demod_amd_survey.h"
+#include "meteor_demod_amd_frames.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
 #endif
@@ -81,6 +85,7 @@ static const struct option longopts[] = {
 	{ "pilot-margin", 1, NULL, 0x04 }, { "carrier-seed", 1, NULL, 0x05 }, { "devices", 1, NULL, 0x06 }, { "plan", 0, NULL, 0x07 },
 	{ "tui-selftest", 0, NULL, 0x08 }, { "tui", 0, NULL, 0x09 }, { "jobs", 1, NULL, 0x0a },
 	{ "offset", 1, NULL, 0x0b },    { "decimate", 1, NULL, 0x0c }, { "scan", 0, NULL, 0x0d },
+	{ "cadu", 0, NULL, 0x0e },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -108,6 +113,16 @@ static int
 have_survey(void)
 {
 	return mdemod_survey_default_opts && mdemod_survey_plan && mdemod_survey_host;
+}
+
+/* the frame layer's entries (include/meteor_demod_amd_frames.h: --cadu): weak as well */
+#pragma weak mdemod_frames_default_opts
+#pragma weak mdemod_frames_decode_host
+
+static int
+have_frames(void)
+{
+	return mdemod_frames_default_opts && mdemod_frames_decode_host;
 }
 
 /* --offset: a signed number of Hz with an optional k / M suffix (fractions kept); 1 on a malformed one */
@@ -177,6 +192,10 @@ usage(const char *prog)
 	        "       --scan              Survey only: one line per candidate of each file on stdout,\n"
 	        "                           offset_hz psd_snr_db clock_quality carrier_quality confirmed\n"
 	        "                           (confirmed ones first, then by psd_snr_db), and exit 0 without demodulating\n"
+	        "       --cadu              Frames as well: after an output file is complete, find and decode its CCSDS frames\n"
+	        "                           on the GPU (sync search, Viterbi) and write them, 1024 bytes each, beside it as\n"
+	        "                           <output>.cadu (.s replaced); one line per file on stdout: frames, flywheel frames,\n"
+	        "                           runs, mean channel errors / 16372.  Not with --stdout\n"
 	        "   -h, --help   -v, --version\n", prog);
 }
 
@@ -663,6 +682,53 @@ survey_file(const mdemod_params *in, const mdemod_survey_opts *so, struct stream
 	return rc;
 }
 
+/* --cadu: the soft symbols of one finished output file through the frame layer, the CADUs beside it.  0, or the exit status. */
+static int
+cadu_file(const char *s_name, int device)
+{
+	FILE *f = fopen(s_name, "rb");
+	if (!f) { fprintf(stderr, "--cadu: %s: %s\n", s_name, strerror(errno)); return 1; }
+	long len = -1;
+	if (!fseek(f, 0, SEEK_END)) len = ftell(f);
+	if (len < 0 || fseek(f, 0, SEEK_SET)) { fprintf(stderr, "--cadu: cannot read %s\n", s_name); fclose(f); return 1; }
+	const uint64_t m = (uint64_t)len / 2, cap = m / MDEMOD_FRAME_SYMBOLS;
+	int8_t *soft = malloc(len ? (size_t)len : 1);
+	uint8_t *cadu = malloc(cap ? (size_t)cap * MDEMOD_FRAME_BYTES : 1);
+	mdemod_frame_info *frames = calloc(cap ? (size_t)cap : 1, sizeof(*frames));
+	const size_t name_len = strlen(s_name);
+	char *out_name = malloc(name_len + 6);
+	int code = 1;
+	if (!soft || !cadu || !frames || !out_name) { fprintf(stderr, "--cadu: out of memory reading %s\n", s_name); goto done; }
+	if (fread(soft, 1, (size_t)len, f) != (size_t)len) { fprintf(stderr, "--cadu: cannot read %s\n", s_name); goto done; }
+	mdemod_frames_opts fo;
+	mdemod_frames_default_opts(&fo);
+	uint64_t n = 0;
+	const int rc = mdemod_frames_decode_host(&fo, soft, m, cadu, frames, cap, &n, device);
+	if (rc != MDEMOD_OK) { fprintf(stderr, "--cadu: %s: %s\n", s_name, why_of(rc)); code = 2; goto done; }
+	if (n > cap) n = cap;
+	strcpy(out_name, s_name);
+	if (name_len > 2 && !strcmp(s_name + name_len - 2, ".s")) out_name[name_len - 2] = 0;
+	strcat(out_name, ".cadu");
+	FILE *o = fopen(out_name, "wb");
+	if (!o) { fprintf(stderr, "--cadu: could not open %s\n", out_name); goto done; }
+	const int short_write = fwrite(cadu, MDEMOD_FRAME_BYTES, (size_t)n, o) != (size_t)n;
+	if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--cadu: writing %s failed: the output is incomplete\n", out_name); goto done; }
+	uint64_t fly = 0, errors = 0;
+	uint32_t runs = 0, last_run = 0;
+	for (uint64_t i = 0; i < n; i++) {
+		fly += frames[i].flags & MDEMOD_FRAME_FLYWHEEL ? 1 : 0;
+		errors += frames[i].channel_errors;
+		if (i == 0 || frames[i].run > last_run) { runs++; last_run = frames[i].run; }     /* (run numbers ascend with the position where runs do not interleave; a run seen again is not counted twice) */
+	}
+	printf("%s: %llu frames (%llu flywheel) in %u runs, mean channel errors %.1f / %d\n", out_name, (unsigned long long)n, (unsigned long long)fly, runs,
+	       n ? (double)errors / (double)n : 0.0, MDEMOD_FRAME_DECISIONS);
+	code = 0;
+done:
+	free(out_name); free(frames); free(cadu); free(soft);
+	fclose(f);
+	return code;
+}
+
 int
 main(int argc, char **argv)
 {
@@ -674,7 +740,7 @@ main(int argc, char **argv)
 	int devs[MAX_DEVICES], n_dev = 0, plan = 0, jobs = 4;
 	int use_fe = 0, decimation = 1;
 	double offset_hz = 0.0;
-	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0;
+	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0;
 	double *auto_offsets = NULL;               /* --offset auto: the offset chosen for each file */
 #ifdef MDEMOD_TUI
 	int force_tui = 0;
@@ -697,6 +763,7 @@ main(int argc, char **argv)
 #endif
 		case 0x0a: jobs = atoi(optarg); if (jobs < 1) { fprintf(stderr, "--jobs: a positive number\n"); return 1; } break;
 		case 0x0d: scan = 1; break;
+		case 0x0e: want_cadu = 1; break;
 		case 0x0b:
 			if (!strcmp(optarg, "auto")) { auto_offset = 1; use_fe = 1; break; }
 			auto_offset = 0;
@@ -761,6 +828,14 @@ main(int argc, char **argv)
 	}
 	if ((auto_offset || auto_decimate || scan) && !have_survey()) {
 		fprintf(stderr, "--offset auto / --decimate auto / --scan: this library has no survey (built without include/meteor_demod_amd_survey.h's entries)\n");
+		return 1;
+	}
+	if (want_cadu && stdout_mode) {
+		fprintf(stderr, "--cadu: not with --stdout (the frames are decoded from the finished output file)\n");
+		return 1;
+	}
+	if (want_cadu && !have_frames()) {
+		fprintf(stderr, "--cadu: this library has no frame layer (built without include/meteor_demod_amd_frames.h's entries)\n");
 		return 1;
 	}
 	if (auto_offset || scan)
@@ -960,5 +1035,7 @@ main(int argc, char **argv)
 	for (int d = 0; d < n_dev; d++) if (ws[d].rc > rc_all) rc_all = ws[d].rc;
 	/* (the workers closed their files through their own copies of the stream_io entries: nothing of the originals is open any more) */
 	for (int i = 0; i < n_files; i++) { io[i].in = NULL; io[i].out = NULL; }
+	if (want_cadu && rc_all == 0)
+		for (int i = 0; i < n_files && rc_all == 0; i++) rc_all = cadu_file(io[i].out_name, devs[i % n_dev]);
 	LEAVE(rc_all);
 }

@@ -9,7 +9,9 @@ from .demod import DemodConfig, Demodulator, derive_tables, scale_freq_max  # no
 from .frontend import FrontEnd, FrontEndConfig, demodulate_recording_frontend, design_taps  # noqa: F401
 from . import survey  # noqa: F401
 from .survey import Hit, survey_plan  # noqa: F401
+from . import frames  # noqa: F401
+from .frames import Frame  # noqa: F401
 
 __all__ = ["DemodConfig", "Demodulator", "derive_tables", "scale_freq_max",
            "FrontEnd", "FrontEndConfig", "demodulate_recording_frontend", "design_taps",
-           "survey", "Hit", "survey_plan"]
+           "survey", "Hit", "survey_plan", "frames", "Frame"]
