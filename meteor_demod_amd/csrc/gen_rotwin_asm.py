@@ -27,6 +27,7 @@ import sys
 WB = 96          # first window register
 CB = None        # coefficient buffers: NBUF x 4 registers below the window (set below)
 NCH = 10         # chunks of 8 slots
+SLIDE = 8        # slots a slide brings in: one chunk
 # coefficient prefetch of the FIR: 0 = one load and one s_waitcnt per half-chunk, three half-chunks ahead; 1 = two loads and one
 # s_waitcnt per chunk, one chunk ahead at the wait (half the s_waitcnt instructions)
 PAIRWAIT = int(os.environ.get("ROTWIN_PAIRWAIT", "1"))
@@ -69,8 +70,12 @@ def fir():
         b = CB + 4 * (h % NBUF)
         return "ds_read_b128 v[%d:%d], %%[addr] offset:%d" % (b, b + 3, 16 * h)
     L = []
+    # filter.c:51: the sum starts from +0 (the first tap ADDS to it: +0 + (-0) = +0).  The accumulator is an output of the statement
+    # and zeroed here, in the prologue every rotation shares: one instruction, and the compiler keeps no zero pair alive for it
     if PK in (0, 2):
         L += ["v_mov_b32 %[ar], 0", "v_mov_b32 %[ai], 0"]
+    else:
+        L += ["v_mov_b64 %[acc], 0"]
     L += [load(h) for h in range(2 * DC if PAIRWAIT else D)]  # on their way before the jump (the same for every rotation)
     L += jump("fir", NCH)
     for r in range(NCH):
@@ -139,7 +144,8 @@ def fir():
 
 def put(kind):
     """16 conversions of 8 raw samples (s16: 8 dwords g0..g7; u8: 4 dwords g0..g3, already xor-ed with 0x80808080) or 16
-    moves of ready floats (f0..f15) into physical chunk %[rot]."""
+    moves of ready floats (f0..f15) into physical chunk %[rot]; then %[rot] becomes the next rotation and %[base] moves on by one
+    slide (callers that only fill a chunk pass scratch copies)."""
     L = ["s_nop 1"] if kind == "u8" else []          # the xor that feeds the SDWA selects may be the instruction before
     L += jump("put", NCH)
     for r in range(NCH):
@@ -156,6 +162,13 @@ def put(kind):
                     L += ["v_mov_b32 v%d, %%[f%d]" % (dst, 2 * s + comp)]
         L += ["s_branch .Lput_end_%="]
     L += [".Lput_end_%=:"]
+    # the slide's bookkeeping on the scalar unit, behind the last conversion: the window's rotation count and the sample position of
+    # logical slot 0 are wave-uniform, and as "+s" operands of this statement they are SGPR definitions the compiler cannot turn
+    # into vector phis (as C++ they lived in VGPRs: v_add / v_cmp / v_cndmask and two v_readfirstlane per slide, one more per firing)
+    L += ["s_add_i32 %%[base], %%[base], %d" % SLIDE,
+          "s_add_i32 %[rot], %[rot], 1",
+          "s_cmp_eq_u32 %%[rot], %d" % NCH,
+          "s_cselect_b32 %[rot], 0, %[rot]"]
     return L
 
 
@@ -243,6 +256,7 @@ def main():
     out.append("#define ROTWIN_CB %d" % CB)
     out.append("#define ROTWIN_LIMIT %d   /* first register the compiler may not use */" % (TB if PK in (2, 3) else CB))
     out.append("#define ROTWIN_NCH %d" % NCH)
+    out.append("#define ROTWIN_SLIDE %d" % SLIDE)
     out.append("#define ROTWIN_AB %d   /* first AccVGPR of the hybrid window's newer half */" % AB)
     out.append("#define ROTWIN_PK %d" % PK)
     out.append("#define ROTWIN_FIR_ASM \\\n" + q(fir()).replace("\n", " \\\n"))

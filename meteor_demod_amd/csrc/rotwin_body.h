@@ -9,6 +9,7 @@
  *     put_history(hist, valid, c)      SLIDE history samples (float pairs) -> chunk c of the window at rotation 0
  *     put_init(granules, c)            SLIDE raw input samples             -> chunk c of the window at rotation 0
  *     put(granules, q)                 the slide: SLIDE raw input samples become the newest chunk, chunk q (the oldest) goes
+ *     slide(granules, rot, base)       (SCALAR_SLIDE policies) put(granules, rot), then rot and base move on by one slide, as scalars
  *     fir(ctab_addr, a, bank, C, rot, re, im)      filter.c:46-65 for a lane whose taps start `a` slots into the window
  * and the geometry (kTaps, kBack, NW, SLIDE, AMAX, MAXSL, BLOCK, ROTN: rotations before the window is where it started,
  * RING: symbols of the per-lane output ring).  Everything else - symbol clock, AGC, NCO, loops, lock
@@ -97,7 +98,7 @@ typedef const __attribute__((address_space(3))) rot_i4 *rot_clktab_t;
 struct RotClockConsts { int k_safe, steps_need, interp; float f_hi; uint32_t magic; float inv; const cj_sched *jump; rot_clktab_t tab; };   /* jump: the launch arguments' two schedules, read where they are used (scalar loads) rather than held in registers; tab: null = this context keeps the arithmetic */
 template <int KS>          /* KS > 0: the number of blind steps is known at compile time (the launcher checks it), 0: any */
 __device__ __forceinline__ void
-rot_clock_fast(const RotClockConsts &K, float thr, int v_end, float &t_phase, float t_freq, int &isub, int &v_cur, int &bank, bool &fired, int jidx = -1)
+rot_clock_fast(const RotClockConsts &K, float thr, int v_end, int v_fast_end, float &t_phase, float t_freq, int &isub, int &v_cur, int &bank, bool &fired, int jidx = -1)
 {
 	int k_safe = KS ? KS : K.k_safe;
 	const int interp = K.interp;
@@ -105,11 +106,12 @@ rot_clock_fast(const RotClockConsts &K, float thr, int v_end, float &t_phase, fl
 	 * run this is (0: from 0, 1: the second rail of an OQPSK symbol, from pi; -1: the caller's lanes are not all on the same one) */
 	const bool jump = KS == 0 && jidx >= 0 && K.jump[jidx < 0 ? 0 : jidx].nb > 0;
 	const cj_sched &J = K.jump[jidx < 0 ? 0 : jidx];
-	/* enough input left for k_safe + 4 steps (the part of the current sample still to be stepped is ignored: conservative) */
+	/* enough input left for k_safe + 4 steps (the part of the current sample still to be stepped is ignored: conservative).  The
+	 * fixed-step clocks ask it of v_fast_end = v_end - K.steps_need, worked out once per lane: one compare, no addition per firing */
 	const bool fast = (KS == 109 ? (t_phase > CJ109_P_LO && t_phase < CJ109_P_HI)
 	                   : jump    ? (t_phase > J.floor && t_phase < J.hi)
 	                             : (t_phase < thr - (float)k_safe * K.f_hi - 1e-3f))
-	                  && (v_cur + (jump ? J.need : K.steps_need) < v_end);
+	                  && (jump ? (v_cur + J.need < v_end) : (v_cur < v_fast_end));
 	if (fast) {
 		float p = t_phase;
 		if (KS == 109) k_safe = clock_jump_109(p, t_freq, thr, K.inv);   /* configs[3]: 30 real additions and three binades in closed form (clock_jump.h) */
@@ -180,7 +182,13 @@ rotwin_demod(const DemodLaunch &L)
 	float *lut = ctab + L.ctab_floats;
 	enum { S_GAIN, S_BIAS_RE, S_BIAS_IM, S_PHASE, S_FREQ, S_ERR, S_FLAGS, S_TPREV, S_INPHASE, S_EVCALL, S_FIRSTLOCK, S_LASTV, S_COUNT };
 	static_assert(S_COUNT == MDEMOD_RW_STATE_SLOTS, "host LDS sizing");
-	float *sl = lut + 32 + (threadIdx.x >> 6) * (S_COUNT * 64) + (threadIdx.x & 63);
+	/* The slots' base is an LDS address the compiler takes as it is: left to itself it keeps the base without the 128 bytes of the
+	 * tanh table in front and folds them into every offset, which the S_ERR / S_FLAGS pair (ds_read2st64 / ds_write2st64: offsets in
+	 * units of 256 bytes) cannot take - an address addition per firing. */
+	uint32_t sl_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)lds
+	                   + 4u * (L.ctab_floats + 32u + (threadIdx.x >> 6) * (uint32_t)(S_COUNT * 64) + (threadIdx.x & 63u));
+	asm("" : "+v"(sl_addr));
+	float *sl = (float *)(__attribute__((address_space(3))) float *)(uintptr_t)sl_addr;
 	int *sli = reinterpret_cast<int *>(sl);
 	uint4 *stage = reinterpret_cast<uint4 *>(lut + 32 + (BLOCK / 64) * (S_COUNT * 64)) + threadIdx.x;
 	const uint32_t ctab_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)lds;
@@ -272,6 +280,9 @@ rotwin_demod(const DemodLaunch &L)
 	 * `emit` branches below are scalar and the I-rail iterations skip that code instead of running it masked off. */
 	int slot = 1;
 	int base = 0;
+	/* (a policy whose slide keeps rot and base as scalars: their first value is a scalar definition too - a plain 0 is the zero the
+	 * compiler already has in a VGPR, and one vector input makes both loop phis vector registers) */
+	if constexpr (W::SCALAR_SLIDE) asm("s_mov_b32 %0, 0\n\ts_mov_b32 %1, 0" : "=s"(rot), "=s"(base));
 	int isub = 0, bank = interp - 1;                       /* bank: filter.c:52's `interp - 1 - interp_idx` of the pending firing */
 	bool fired = false;
 	bool done = !valid || n == 0;
@@ -286,6 +297,11 @@ rotwin_demod(const DemodLaunch &L)
 	K.steps_need = ((KS == 109 ? CJ109_MAX_STEPS : C.step_safe) + 4 + C.interp - 1) / C.interp;      /* samples that hold k_safe + 4 steps */
 	K.jump = C.jump;
 	K.tab = has_clktab ? (rot_clktab_t)clktab : (rot_clktab_t)0;
+	const int v_fast_end = v_end - K.steps_need;           /* rot_clock_fast: the last position with a whole fast step's input */
+	/* the loop filters' gains and the clock's centre are operands of plain VOP2 instructions of the scalar stage; a policy with
+	 * registers to spare (W::VCONST) holds them in VGPRs - the empty statement hides that they are wave-uniform */
+	float k_t_alpha = C.t_alpha, k_t_beta = C.t_beta, k_t_center = C.t_center, k_pll_alpha = C.pll_alpha, k_pll_beta = C.pll_beta;
+	if constexpr (W::VCONST) asm("" : "+v"(k_t_alpha), "+v"(k_t_beta), "+v"(k_t_center), "+v"(k_pll_alpha), "+v"(k_pll_beta));
 
 	int n_wave_max = n;
 	for (int o = 32; o > 0; o >>= 1) {
@@ -309,7 +325,7 @@ rotwin_demod(const DemodLaunch &L)
 		 * lanes that ran ahead of the window.  A lane that fires does its next clock inside the firing (below). ---- */
 		if (!fired && !done) {
 			const float thr = OQPSK ? (float)dual_state * MD_PI_F : MD_TWO_PI_F;
-			rot_clock_fast<KS>(K, thr, v_end, t_phase, t_freq, isub, v_cur, bank, fired);
+			rot_clock_fast<KS>(K, thr, v_end, v_fast_end, t_phase, t_freq, isub, v_cur, bank, fired);
 			while (!fired && !done) {
 				if (isub == 0) {
 					if (v_cur + 1 >= v_end) { done = true; v_cur = V_DONE; break; }
@@ -339,9 +355,12 @@ rotwin_demod(const DemodLaunch &L)
 				RGran<FMT> g[GPS];
 #pragma unroll
 				for (int i = 0; i < GPS; i++) g[i] = stg[i];
-				win.put(g, __builtin_amdgcn_readfirstlane(rot));
-				rot = __builtin_amdgcn_readfirstlane((rot == ROTN - 1) ? 0 : rot + 1);      /* wave-uniform: keep them in SGPRs */
-				base = __builtin_amdgcn_readfirstlane(base + SLIDE);
+				if constexpr (W::SCALAR_SLIDE) win.slide(g, rot, base);    /* rot and base move on inside the slide's assembly: real scalars */
+				else {
+					win.put(g, __builtin_amdgcn_readfirstlane(rot));
+					rot = __builtin_amdgcn_readfirstlane((rot == ROTN - 1) ? 0 : rot + 1);      /* wave-uniform */
+					base = __builtin_amdgcn_readfirstlane(base + SLIDE);
+				}
 #pragma unroll
 				for (int i = 0; i + GPS < NST; i++) stg[i] = stg[i + GPS];
 				const int m_new = 4 * g_load;
@@ -364,7 +383,7 @@ rotwin_demod(const DemodLaunch &L)
 			fired = false;
 			cf32 y;
 			if constexpr (GATHER) win.fir_gather(ctab_addr, src, hist_in, v_cur, n, bank, C, y.re, y.im);
-			else win.fir(ctab_addr, a, bank, C, __builtin_amdgcn_readfirstlane(rot), y.re, y.im);
+			else win.fir(ctab_addr, a, bank, C, W::SCALAR_SLIDE ? rot : __builtin_amdgcn_readfirstlane(rot), y.re, y.im);
 			if (PRIO) __builtin_amdgcn_s_setprio(ROT_PRIO_LEVEL);
 			ROT_TICK(2);
 #ifdef ROT_EXP_TIMING            /* (tools/build_exp_rot.sh, tools/pmc_shape.py: see above) */
@@ -406,12 +425,12 @@ rotwin_demod(const DemodLaunch &L)
 				st_lastv(v_cur);
 				if (__builtin_expect(md_any(again), 0)) { if (again) sym_call--; }
 				float t_prev = ld_tprev();
-				md_timing_update(t_phase, t_freq, t_prev, C.t_alpha, C.t_beta, C.t_center, C.t_maxdev, out_im);
+				md_timing_update(t_phase, t_freq, t_prev, k_t_alpha, k_t_beta, k_t_center, C.t_maxdev, out_im);
 				st_tprev(t_prev);
 			}
 			/* the clock's way to the NEXT firing starts here: a chain of ~20 dependent adds that needs nothing but the timing
 			 * update, next to the Costas update, the AGC's square root and the quantiser, which need nothing from it */
-			rot_clock_fast<KS>(K, OQPSK ? (float)dual_state * MD_PI_F : MD_TWO_PI_F, v_end, t_phase, t_freq, isub, v_cur, bank, fired,
+			rot_clock_fast<KS>(K, OQPSK ? (float)dual_state * MD_PI_F : MD_TWO_PI_F, v_end, v_fast_end, t_phase, t_freq, isub, v_cur, bank, fired,
 			                   OQPSK ? (ROT_OQ_SYNC ? 2 - slot : -1) : 0);
 #ifdef ROT_EXP_TIMING            /* (tools/build_exp_rot.sh, tools/pmc_shape.py: see above) */
 			if (!fired) n_slide++;                     /* (experiment: lanes the fast clock left to the stepping loop) */
@@ -419,7 +438,7 @@ rotwin_demod(const DemodLaunch &L)
 #endif
 			if (emit) {
 				uint32_t first = 0;
-				const uint32_t changed = md_pll_update_packed(pll, fl, lut, C.pll_alpha, C.pll_beta, C.pll_fmax, out_re, out_im, first);
+				const uint32_t changed = md_pll_update_packed(pll, fl, lut, k_pll_alpha, k_pll_beta, C.pll_fmax, out_re, out_im, first);
 				if (__builtin_expect(changed != 0, 0)) {          /* a plain divergent branch: skipped when no lane of the wave takes it */
 					if (first) sli[S_FIRSTLOCK * 64] = (int)sym_call;
 					const int ev_call = sli[S_EVCALL * 64];
