@@ -34,6 +34,9 @@
  * --cadu runs the frame layer (include/meteor_demod_amd_frames.h) over every output file once it is complete and closed: sync
  * search and Viterbi decoding on the GPU, the CADUs (1024 bytes each) into <output without .s>.cadu, one line about them on stdout.
  * Weak references again; refused with --stdout.
+ * --vcdu goes on from there (include/meteor_demod_amd_rs.h): the CADUs derandomised and Reed-Solomon corrected on the GPU, the VCDUs
+ * (892 bytes each, uncorrectable frames included) into <output without .s>.vcdu, one more line on stdout.  It implies the frame
+ * pass; the .cadu is written only when --cadu is given too.  Weak references; refused with --stdout.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -53,6 +56,7 @@
 #include "meteor_demod_amd_frontend.h"
 #include "meteor_demod_amd_survey.h"
 #include "meteor_demod_amd_frames.h"
+#include "meteor_demod_amd_rs.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
 #endif
@@ -85,7 +89,7 @@ static const struct option longopts[] = {
 	{ "pilot-margin", 1, NULL, 0x04 }, { "carrier-seed", 1, NULL, 0x05 }, { "devices", 1, NULL, 0x06 }, { "plan", 0, NULL, 0x07 },
 	{ "tui-selftest", 0, NULL, 0x08 }, { "tui", 0, NULL, 0x09 }, { "jobs", 1, NULL, 0x0a },
 	{ "offset", 1, NULL, 0x0b },    { "decimate", 1, NULL, 0x0c }, { "scan", 0, NULL, 0x0d },
-	{ "cadu", 0, NULL, 0x0e },
+	{ "cadu", 0, NULL, 0x0e },      { "vcdu", 0, NULL, 0x0f },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -123,6 +127,17 @@ static int
 have_frames(void)
 {
 	return mdemod_frames_default_opts && mdemod_frames_decode_host;
+}
+
+/* the transfer-frame layer's entries (include/meteor_demod_amd_rs.h: --vcdu): weak as well */
+#pragma weak mdemod_rs_default_opts
+#pragma weak mdemod_rs_decode_host
+#pragma weak mdemod_rs_vcdu_header
+
+static int
+have_rs(void)
+{
+	return mdemod_rs_default_opts && mdemod_rs_decode_host && mdemod_rs_vcdu_header;
 }
 
 /* --offset: a signed number of Hz with an optional k / M suffix (fractions kept); 1 on a malformed one */
@@ -196,6 +211,11 @@ usage(const char *prog)
 	        "                           on the GPU (sync search, Viterbi) and write them, 1024 bytes each, beside it as\n"
 	        "                           <output>.cadu (.s replaced); one line per file on stdout: frames, flywheel frames,\n"
 	        "                           runs, mean channel errors / 16372.  Not with --stdout\n"
+	        "       --vcdu              Transfer frames as well: the frames of --cadu derandomised and Reed-Solomon corrected\n"
+	        "                           on the GPU, written 892 bytes each as <output>.vcdu (uncorrectable frames included:\n"
+	        "                           frame i of the .vcdu is frame i of the .cadu); one more line on stdout: frames,\n"
+	        "                           uncorrectable frames, bytes corrected, frames and counter gaps per VCID.  The .cadu\n"
+	        "                           is written only with --cadu.  Not with --stdout\n"
 	        "   -h, --help   -v, --version\n", prog);
 }
 
@@ -682,9 +702,67 @@ survey_file(const mdemod_params *in, const mdemod_survey_opts *so, struct stream
 	return rc;
 }
 
-/* --cadu: the soft symbols of one finished output file through the frame layer, the CADUs beside it.  0, or the exit status. */
+/* <s_name without .s><ext> in a new string (NULL: out of memory) */
+static char *
+beside(const char *s_name, const char *ext)
+{
+	const size_t name_len = strlen(s_name);
+	char *out = malloc(name_len + strlen(ext) + 1);
+	if (!out) return NULL;
+	strcpy(out, s_name);
+	if (name_len > 2 && !strcmp(s_name + name_len - 2, ".s")) out[name_len - 2] = 0;
+	strcat(out, ext);
+	return out;
+}
+
+/* --vcdu: n CADUs through the transfer-frame layer, the VCDUs beside the output file, one line.  0, or the exit status. */
 static int
-cadu_file(const char *s_name, int device)
+vcdu_file(const char *s_name, const uint8_t *cadu, uint64_t n, int device)
+{
+	uint8_t *vcdu = malloc(n ? (size_t)n * MDEMOD_RS_VCDU_BYTES : 1);
+	mdemod_rs_info *info = calloc(n ? (size_t)n : 1, sizeof(*info));
+	char *out_name = beside(s_name, ".vcdu");
+	int code = 1;
+	if (!vcdu || !info || !out_name) { fprintf(stderr, "--vcdu: out of memory for the frames of %s\n", s_name); goto done; }
+	mdemod_rs_opts ro;
+	mdemod_rs_default_opts(&ro);
+	const int rc = mdemod_rs_decode_host(&ro, cadu, n, vcdu, info, device);
+	if (rc != MDEMOD_OK) { fprintf(stderr, "--vcdu: %s: %s\n", s_name, why_of(rc)); code = 2; goto done; }
+	FILE *o = fopen(out_name, "wb");
+	if (!o) { fprintf(stderr, "--vcdu: could not open %s\n", out_name); goto done; }
+	const int short_write = fwrite(vcdu, MDEMOD_RS_VCDU_BYTES, (size_t)n, o) != (size_t)n;
+	if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--vcdu: writing %s failed: the output is incomplete\n", out_name); goto done; }
+	/* per VCID, over the frames without an uncorrectable codeword: frames, and places where the counter does not follow */
+	uint64_t lost = 0, fixed = 0, per[64] = { 0 }, gaps[64] = { 0 };
+	uint32_t last[64];
+	int seen[64] = { 0 };
+	for (uint64_t i = 0; i < n; i++) {
+		for (int c = 0; c < 4; c++)
+			if (info[i].corrected[c] != MDEMOD_RS_FAILED) fixed += info[i].corrected[c];
+		if (info[i].flags & MDEMOD_RS_UNCORRECTABLE) { lost++; continue; }
+		mdemod_rs_header h;
+		mdemod_rs_vcdu_header(vcdu + i * MDEMOD_RS_VCDU_BYTES, &h);
+		const uint32_t v = h.vcid & 63u;
+		per[v]++;
+		if (seen[v] && h.counter != ((last[v] + 1) & 0xFFFFFFu)) gaps[v]++;
+		seen[v] = 1;
+		last[v] = h.counter;
+	}
+	printf("%s: %llu frames, %llu uncorrectable, %llu bytes corrected;", out_name, (unsigned long long)n, (unsigned long long)lost, (unsigned long long)fixed);
+	int any = 0;
+	for (int v = 0; v < 64; v++)
+		if (seen[v]) { printf("%s vcid %d: %llu frames, %llu counter gaps", any ? "," : "", v, (unsigned long long)per[v], (unsigned long long)gaps[v]); any = 1; }
+	printf("%s\n", any ? "" : " no VCID");
+	code = 0;
+done:
+	free(out_name); free(info); free(vcdu);
+	return code;
+}
+
+/* --cadu / --vcdu: the soft symbols of one finished output file through the frame layer, the CADUs (and the VCDUs) beside it.  0, or
+ * the exit status. */
+static int
+cadu_file(const char *s_name, int device, int write_cadu, int write_vcdu)
 {
 	FILE *f = fopen(s_name, "rb");
 	if (!f) { fprintf(stderr, "--cadu: %s: %s\n", s_name, strerror(errno)); return 1; }
@@ -695,8 +773,7 @@ cadu_file(const char *s_name, int device)
 	int8_t *soft = malloc(len ? (size_t)len : 1);
 	uint8_t *cadu = malloc(cap ? (size_t)cap * MDEMOD_FRAME_BYTES : 1);
 	mdemod_frame_info *frames = calloc(cap ? (size_t)cap : 1, sizeof(*frames));
-	const size_t name_len = strlen(s_name);
-	char *out_name = malloc(name_len + 6);
+	char *out_name = beside(s_name, ".cadu");
 	int code = 1;
 	if (!soft || !cadu || !frames || !out_name) { fprintf(stderr, "--cadu: out of memory reading %s\n", s_name); goto done; }
 	if (fread(soft, 1, (size_t)len, f) != (size_t)len) { fprintf(stderr, "--cadu: cannot read %s\n", s_name); goto done; }
@@ -706,9 +783,7 @@ cadu_file(const char *s_name, int device)
 	const int rc = mdemod_frames_decode_host(&fo, soft, m, cadu, frames, cap, &n, device);
 	if (rc != MDEMOD_OK) { fprintf(stderr, "--cadu: %s: %s\n", s_name, why_of(rc)); code = 2; goto done; }
 	if (n > cap) n = cap;
-	strcpy(out_name, s_name);
-	if (name_len > 2 && !strcmp(s_name + name_len - 2, ".s")) out_name[name_len - 2] = 0;
-	strcat(out_name, ".cadu");
+	if (!write_cadu) { code = vcdu_file(s_name, cadu, n, device); goto done; }
 	FILE *o = fopen(out_name, "wb");
 	if (!o) { fprintf(stderr, "--cadu: could not open %s\n", out_name); goto done; }
 	const int short_write = fwrite(cadu, MDEMOD_FRAME_BYTES, (size_t)n, o) != (size_t)n;
@@ -722,7 +797,7 @@ cadu_file(const char *s_name, int device)
 	}
 	printf("%s: %llu frames (%llu flywheel) in %u runs, mean channel errors %.1f / %d\n", out_name, (unsigned long long)n, (unsigned long long)fly, runs,
 	       n ? (double)errors / (double)n : 0.0, MDEMOD_FRAME_DECISIONS);
-	code = 0;
+	code = write_vcdu ? vcdu_file(s_name, cadu, n, device) : 0;
 done:
 	free(out_name); free(frames); free(cadu); free(soft);
 	fclose(f);
@@ -740,7 +815,7 @@ main(int argc, char **argv)
 	int devs[MAX_DEVICES], n_dev = 0, plan = 0, jobs = 4;
 	int use_fe = 0, decimation = 1;
 	double offset_hz = 0.0;
-	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0;
+	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0, want_vcdu = 0;
 	double *auto_offsets = NULL;               /* --offset auto: the offset chosen for each file */
 #ifdef MDEMOD_TUI
 	int force_tui = 0;
@@ -764,6 +839,7 @@ main(int argc, char **argv)
 		case 0x0a: jobs = atoi(optarg); if (jobs < 1) { fprintf(stderr, "--jobs: a positive number\n"); return 1; } break;
 		case 0x0d: scan = 1; break;
 		case 0x0e: want_cadu = 1; break;
+		case 0x0f: want_vcdu = 1; break;
 		case 0x0b:
 			if (!strcmp(optarg, "auto")) { auto_offset = 1; use_fe = 1; break; }
 			auto_offset = 0;
@@ -836,6 +912,15 @@ main(int argc, char **argv)
 	}
 	if (want_cadu && !have_frames()) {
 		fprintf(stderr, "--cadu: this library has no frame layer (built without include/meteor_demod_amd_frames.h's entries)\n");
+		return 1;
+	}
+	if (want_vcdu && stdout_mode) {
+		fprintf(stderr, "--vcdu: not with --stdout (the frames are decoded from the finished output file)\n");
+		return 1;
+	}
+	if (want_vcdu && !(have_frames() && have_rs())) {
+		fprintf(stderr, "--vcdu: this library has no %s (built without include/%s's entries)\n", have_frames() ? "transfer-frame layer" : "frame layer",
+		        have_frames() ? "meteor_demod_amd_rs.h" : "meteor_demod_amd_frames.h");
 		return 1;
 	}
 	if (auto_offset || scan)
@@ -1035,7 +1120,7 @@ main(int argc, char **argv)
 	for (int d = 0; d < n_dev; d++) if (ws[d].rc > rc_all) rc_all = ws[d].rc;
 	/* (the workers closed their files through their own copies of the stream_io entries: nothing of the originals is open any more) */
 	for (int i = 0; i < n_files; i++) { io[i].in = NULL; io[i].out = NULL; }
-	if (want_cadu && rc_all == 0)
-		for (int i = 0; i < n_files && rc_all == 0; i++) rc_all = cadu_file(io[i].out_name, devs[i % n_dev]);
+	if ((want_cadu || want_vcdu) && rc_all == 0)
+		for (int i = 0; i < n_files && rc_all == 0; i++) rc_all = cadu_file(io[i].out_name, devs[i % n_dev], want_cadu, want_vcdu);
 	LEAVE(rc_all);
 }

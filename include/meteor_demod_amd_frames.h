@@ -5,7 +5,7 @@
  * frames in such a stream (a correlation with the encoded sync marker at every symbol position, GPU), follows them (a tracker, host
  * code without GPU) and decodes them (Viterbi, GPU), and says for every frame how many channel bits the decoder corrected.
  * QPSK framing only.  NOT here: differential coding, the 80 k interleaved mode, a one-symbol skew between the rails (OQPSK at odd
- * rotations), derandomising, Reed-Solomon.
+ * rotations).  Derandomising and Reed-Solomon follow in include/meteor_demod_amd_rs.h.
  * The specification of the kernels is a host model (csrc/frames_host.cpp, exported as mdemod_frames_model_*, csrc/frames_host.h):
  * everything is integer arithmetic, and GPU bytes equal model bytes.
  *

@@ -11,7 +11,9 @@ from . import survey  # noqa: F401
 from .survey import Hit, survey_plan  # noqa: F401
 from . import frames  # noqa: F401
 from .frames import Frame  # noqa: F401
+from . import rs  # noqa: F401
+from .rs import RsInfo  # noqa: F401
 
 __all__ = ["DemodConfig", "Demodulator", "derive_tables", "scale_freq_max",
            "FrontEnd", "FrontEndConfig", "demodulate_recording_frontend", "design_taps",
-           "survey", "Hit", "survey_plan", "frames", "Frame"]
+           "survey", "Hit", "survey_plan", "frames", "Frame", "rs", "RsInfo"]
