@@ -37,6 +37,8 @@
  * --vcdu goes on from there (include/meteor_demod_amd_rs.h): the CADUs derandomised and Reed-Solomon corrected on the GPU, the VCDUs
  * (892 bytes each, uncorrectable frames included) into <output without .s>.vcdu, one more line on stdout.  It implies the frame
  * pass; the .cadu is written only when --cadu is given too.  Weak references; refused with --stdout.
+ * --diff and --skew choose the link variant of the frame pass (include/meteor_demod_amd_frames_link.h: NRZ-M coding, a one-symbol
+ * skew between the rails): what Meteor-M N2-3 / N2-4 need with -m oqpsk.  Only with --cadu / --vcdu.  Weak references.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -56,6 +58,7 @@
 #include "meteor_demod_amd_frontend.h"
 #include "meteor_demod_amd_survey.h"
 #include "meteor_demod_amd_frames.h"
+#include "meteor_demod_amd_frames_link.h"
 #include "meteor_demod_amd_rs.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
@@ -89,7 +92,7 @@ static const struct option longopts[] = {
 	{ "pilot-margin", 1, NULL, 0x04 }, { "carrier-seed", 1, NULL, 0x05 }, { "devices", 1, NULL, 0x06 }, { "plan", 0, NULL, 0x07 },
 	{ "tui-selftest", 0, NULL, 0x08 }, { "tui", 0, NULL, 0x09 }, { "jobs", 1, NULL, 0x0a },
 	{ "offset", 1, NULL, 0x0b },    { "decimate", 1, NULL, 0x0c }, { "scan", 0, NULL, 0x0d },
-	{ "cadu", 0, NULL, 0x0e },      { "vcdu", 0, NULL, 0x0f },
+	{ "cadu", 0, NULL, 0x0e },      { "vcdu", 0, NULL, 0x0f },    { "diff", 0, NULL, 0x10 },    { "skew", 0, NULL, 0x11 },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -127,6 +130,15 @@ static int
 have_frames(void)
 {
 	return mdemod_frames_default_opts && mdemod_frames_decode_host;
+}
+
+/* the frame layer's link variant (include/meteor_demod_amd_frames_link.h: --diff, --skew): weak as well */
+#pragma weak mdemod_frames_link_decode_host
+
+static int
+have_frames_link(void)
+{
+	return mdemod_frames_link_decode_host != NULL;
 }
 
 /* the transfer-frame layer's entries (include/meteor_demod_amd_rs.h: --vcdu): weak as well */
@@ -216,6 +228,11 @@ usage(const char *prog)
 	        "                           frame i of the .vcdu is frame i of the .cadu); one more line on stdout: frames,\n"
 	        "                           uncorrectable frames, bytes corrected, frames and counter gaps per VCID.  The .cadu\n"
 	        "                           is written only with --cadu.  Not with --stdout\n"
+	        "       --diff              With --cadu / --vcdu: the sender codes differentially (NRZ-M); the frame pass searches\n"
+	        "                           the differential marker and undoes the coding after the Viterbi decoder\n"
+	        "       --skew              With --cadu / --vcdu: the rails may stand one symbol apart, as after -m oqpsk when\n"
+	        "                           the carrier loop settles a quarter turn off; the frame pass tries both skews as well.\n"
+	        "                           Meteor-M N2-3 / N2-4 (72k OQPSK) want: -m oqpsk --skew --diff\n"
 	        "   -h, --help   -v, --version\n", prog);
 }
 
@@ -762,7 +779,7 @@ done:
 /* --cadu / --vcdu: the soft symbols of one finished output file through the frame layer, the CADUs (and the VCDUs) beside it.  0, or
  * the exit status. */
 static int
-cadu_file(const char *s_name, int device, int write_cadu, int write_vcdu)
+cadu_file(const char *s_name, int device, int write_cadu, int write_vcdu, int diff, int skew)
 {
 	FILE *f = fopen(s_name, "rb");
 	if (!f) { fprintf(stderr, "--cadu: %s: %s\n", s_name, strerror(errno)); return 1; }
@@ -780,7 +797,9 @@ cadu_file(const char *s_name, int device, int write_cadu, int write_vcdu)
 	mdemod_frames_opts fo;
 	mdemod_frames_default_opts(&fo);
 	uint64_t n = 0;
-	const int rc = mdemod_frames_decode_host(&fo, soft, m, cadu, frames, cap, &n, device);
+	mdemod_frames_link link = { (uint32_t)diff, (uint32_t)skew, { 0, 0 } };
+	const int rc = diff || skew ? mdemod_frames_link_decode_host(&link, &fo, soft, m, cadu, frames, cap, &n, device)
+	                            : mdemod_frames_decode_host(&fo, soft, m, cadu, frames, cap, &n, device);
 	if (rc != MDEMOD_OK) { fprintf(stderr, "--cadu: %s: %s\n", s_name, why_of(rc)); code = 2; goto done; }
 	if (n > cap) n = cap;
 	if (!write_cadu) { code = vcdu_file(s_name, cadu, n, device); goto done; }
@@ -815,7 +834,7 @@ main(int argc, char **argv)
 	int devs[MAX_DEVICES], n_dev = 0, plan = 0, jobs = 4;
 	int use_fe = 0, decimation = 1;
 	double offset_hz = 0.0;
-	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0, want_vcdu = 0;
+	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0, want_vcdu = 0, want_diff = 0, want_skew = 0;
 	double *auto_offsets = NULL;               /* --offset auto: the offset chosen for each file */
 #ifdef MDEMOD_TUI
 	int force_tui = 0;
@@ -840,6 +859,8 @@ main(int argc, char **argv)
 		case 0x0d: scan = 1; break;
 		case 0x0e: want_cadu = 1; break;
 		case 0x0f: want_vcdu = 1; break;
+		case 0x10: want_diff = 1; break;
+		case 0x11: want_skew = 1; break;
 		case 0x0b:
 			if (!strcmp(optarg, "auto")) { auto_offset = 1; use_fe = 1; break; }
 			auto_offset = 0;
@@ -921,6 +942,14 @@ main(int argc, char **argv)
 	if (want_vcdu && !(have_frames() && have_rs())) {
 		fprintf(stderr, "--vcdu: this library has no %s (built without include/%s's entries)\n", have_frames() ? "transfer-frame layer" : "frame layer",
 		        have_frames() ? "meteor_demod_amd_rs.h" : "meteor_demod_amd_frames.h");
+		return 1;
+	}
+	if ((want_diff || want_skew) && !(want_cadu || want_vcdu)) {
+		fprintf(stderr, "--diff / --skew: only with --cadu or --vcdu (they change how the frames are found and decoded, not the soft symbols)\n");
+		return 1;
+	}
+	if ((want_diff || want_skew) && !have_frames_link()) {
+		fprintf(stderr, "--diff / --skew: this library has no link variant of the frame layer (built without include/meteor_demod_amd_frames_link.h's entries)\n");
 		return 1;
 	}
 	if (auto_offset || scan)
@@ -1121,6 +1150,6 @@ main(int argc, char **argv)
 	/* (the workers closed their files through their own copies of the stream_io entries: nothing of the originals is open any more) */
 	for (int i = 0; i < n_files; i++) { io[i].in = NULL; io[i].out = NULL; }
 	if ((want_cadu || want_vcdu) && rc_all == 0)
-		for (int i = 0; i < n_files && rc_all == 0; i++) rc_all = cadu_file(io[i].out_name, devs[i % n_dev], want_cadu, want_vcdu);
+		for (int i = 0; i < n_files && rc_all == 0; i++) rc_all = cadu_file(io[i].out_name, devs[i % n_dev], want_cadu, want_vcdu, want_diff, want_skew);
 	LEAVE(rc_all);
 }

@@ -4,8 +4,9 @@
  * The demodulator (include/meteor_demod_amd.h) ends in int8 soft symbols, as a `.s` file holds them.  The frame layer finds the
  * frames in such a stream (a correlation with the encoded sync marker at every symbol position, GPU), follows them (a tracker, host
  * code without GPU) and decodes them (Viterbi, GPU), and says for every frame how many channel bits the decoder corrected.
- * QPSK framing only.  NOT here: differential coding, the 80 k interleaved mode, a one-symbol skew between the rails (OQPSK at odd
- * rotations).  Derandomising and Reed-Solomon follow in include/meteor_demod_amd_rs.h.
+ * The entries below are QPSK framing.  Differential coding and a one-symbol skew between the rails (OQPSK at odd rotations: Meteor-M
+ * N2-3 / N2-4) are the "link variant" specified at the end of this block; its entries are in include/meteor_demod_amd_frames_link.h.
+ * NOT here: the 80 k interleaved mode.  Derandomising and Reed-Solomon follow in include/meteor_demod_amd_rs.h.
  * The specification of the kernels is a host model (csrc/frames_host.cpp, exported as mdemod_frames_model_*, csrc/frames_host.h):
  * everything is integer arithmetic, and GPU bytes equal model bytes.
  *
@@ -42,6 +43,25 @@
  *   report      per frame: position, hypothesis, score, flags, run, and channel_errors: the number of hard decisions (soft value
  *               through h > 0) that differ from the re-encoded decoded bits, over info bits 6..8191 of the frame (16372
  *               decisions), the encoder state taken from the frame's own first 6 decoded bits.
+ *
+ * The link variant (two switches, `differential` and `skew`; both off: everything above, byte for byte).  No off-air recording of
+ * N2-3 / N2-4 was at hand: what binds is this text, a synthetic sender built to it and the OQPSK demodulator.
+ *   differential  the sender's information bits b pass through NRZ-M before the encoder: d[t] = b[t] xor d[t-1]; the encoder sees d,
+ *               the marker is coded like everything else.  Both generator masks have an odd number of taps, so
+ *               encode(~d) = ~encode(d): polarity is only a sign.
+ *   pattern     with `differential`: the 26 symbols at offsets 6..31 of the marker's 32 bits run through NRZ-M from d[-1] = 0 and
+ *               encoded (derived from the encoder; d[-1] = 1 gives the complement).  The score of a position is |score| under this
+ *               pattern, and only h in {0, 1, 4, 5} are reported: each 180 degree partner describes the same decoding.
+ *   skew        the combined hypothesis is H = h + 8 s: s = 0 no skew; s = 1 symbol n is (I'[n], Q'[n+1]); s = 2 symbol n is
+ *               (I'[n+1], Q'[n]), I' and Q' being the stream through h.  A rail value read at index m, one past the end, is 0.
+ *               With `skew`, positions are p in [0, m - 33), there are ceil((m - 33) / 8192) windows, and all 24 H compete (the 12
+ *               with h in {0, 1, 4, 5} with `differential`); ties go to the lowest p, then the lowest H.  Without `skew`:
+ *               [0, m - 32) and H < 8, as above.
+ *   tracker     unchanged, over (r, H): a skew change starts a new run as a rotation change does.
+ *   decoding    as above with the symbols taken through H.  With `differential` the output bit of step t is d[t] xor d[t-1], with
+ *               d[t-1] from the same sub-block's traceback (the 128-symbol lead-in supplies it; where the lead-in is clamped away,
+ *               sub-block start 0, the bit before step 0 is 0).  Sub-blocks stay independent.  channel_errors is counted on d,
+ *               before the xor, exactly as above.
  */
 #ifndef METEOR_DEMOD_AMD_FRAMES_H
 #define METEOR_DEMOD_AMD_FRAMES_H
@@ -75,12 +95,19 @@ typedef struct {
 typedef struct {
 	uint64_t position;            /* first symbol of the frame                                                                    */
 	int32_t  score;               /* the candidate's; 0 for a flywheel frame                                                      */
-	uint32_t hypothesis;
+	uint32_t hypothesis;          /* 0..7; H = h + 8 s (below 24) from and to the link entries                                    */
 	uint32_t flags;               /* MDEMOD_FRAME_FLYWHEEL                                                                        */
 	uint32_t channel_errors;      /* of 16372; written by the decoding entries (0 from mdemod_frames_track)                        */
 	uint32_t run;                 /* frames of one (merged) run share it: 0, 1, ... in the order the runs begin                   */
 	uint32_t reserved;
 } mdemod_frame_info;
+
+/* The link variant's switches (include/meteor_demod_amd_frames_link.h).  All zero: the layer as the entries below compute it. */
+typedef struct {
+	uint32_t differential;        /* 1: NRZ-M coded sender (differential pattern, |score|, d[t] xor d[t-1] at traceback)                */
+	uint32_t skew;                /* 1: the rails may stand one symbol apart: H = h + 8 s competes, s = 0, 1, 2                          */
+	uint32_t reserved[2];         /* 0                                                                                                  */
+} mdemod_frames_link;
 
 /* min_run 3, flywheel 4, piece_symbols 0. */
 void     mdemod_frames_default_opts(mdemod_frames_opts *opts);

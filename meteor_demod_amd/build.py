@@ -169,6 +169,7 @@ def build(force: bool = False, verbose: bool = False) -> dict[str, Path]:
              (CSRC / "frontend.hip", "frontend", []), (CSRC / "frontend_design.cpp", "frontend_design", []),
              (CSRC / "survey.hip", "survey", []), (CSRC / "survey_detect.cpp", "survey_detect", []),
              (CSRC / "frames.hip", "frames", []), (CSRC / "frames_host.cpp", "frames_host", []),
+             (CSRC / "frames_link.hip", "frames_link", []), (CSRC / "frames_link_host.cpp", "frames_link_host", []),
              (CSRC / "rs.hip", "rs", []), (CSRC / "rs_host.cpp", "rs_host", [])]
     # the assembly of the rotating register window is generated (csrc/gen_rotwin_asm.py -> csrc/rotwin_asm.h)
     for gen, inc in ((CSRC / "gen_rotwin_asm.py", CSRC / "rotwin_asm.h"), (CSRC / "gen_rotpk_asm.py", CSRC / "rotpk_asm.h")):

@@ -1,7 +1,8 @@
 /*
  * frames_host.cpp — host side of the frame layer (include/meteor_demod_amd_frames.h): the pattern, the tracker that serves the
  * product, and the host model of the two kernels of csrc/frames.hip (mdemod_frames_model_*: the kernels' specification, written
- * for reading, one core, no tricks).  HIP-free.
+ * for reading, one core, no tricks).  The arithmetic takes a mode (FrMode: differential, skew) for the link variant, whose
+ * entries are in csrc/frames_link_host.cpp; with both switches off it is the plain layer's.  HIP-free.
  */
 #include <algorithm>
 #include <cstring>
@@ -25,32 +26,23 @@ inline uint32_t enc_step(uint32_t reg, uint32_t bit) { return ((reg << 1) | bit)
 inline int enc_c1(uint32_t reg) { return parity(reg & 0x4Fu) ? 1 : -1; }
 inline int enc_c2(uint32_t reg) { return parity(reg & 0x6Du) ? 1 : -1; }
 
-/* soft symbol i through hypothesis h, in int32 */
+/* symbol i of soft[m][2] through the combined hypothesis H = h + 8 s, in int32: I' and Q' are the stream through h; s = 1 reads
+ * (I'[i], Q'[i + 1]), s = 2 (I'[i + 1], Q'[i]); a rail value at index m is 0 */
 inline void
-through(const int8_t *soft, uint64_t i, const FrHyp &y, int &ip, int &qp)
+through(const int8_t *soft, uint64_t m, uint64_t i, uint32_t H, int &ip, int &qp)
 {
-	const int I = soft[2 * i], Q = soft[2 * i + 1];
-	ip = y.si * (y.swap ? Q : I);
-	qp = y.sq * (y.swap ? I : Q);
+	const FrHyp y = fr_hyp(H & 7u);
+	const uint32_t s = H >> 3;
+	const uint64_t ii = i + (s == 2), qi = i + (s == 1);
+	ip = ii < m ? y.si * soft[2 * ii + (y.swap ? 1 : 0)] : 0;
+	qp = qi < m ? y.sq * soft[2 * qi + (y.swap ? 0 : 1)] : 0;
 }
 
-int
-check_frames(const mdemod_frame_info *frames, uint64_t n_frames, uint64_t m)
-{
-	for (uint64_t f = 0; f < n_frames; f++) {
-		if (frames[f].hypothesis > 7) REFUSE("frames: frame %llu has hypothesis %u (0..7)", (unsigned long long)f, frames[f].hypothesis);
-		if (frames[f].position > m || m - frames[f].position < FR_FRAME)
-			REFUSE("frames: frame %llu at symbol %llu is not complete in a stream of %llu symbols", (unsigned long long)f,
-			       (unsigned long long)frames[f].position, (unsigned long long)m);
-	}
-	return MDEMOD_OK;
-}
-
-/* one sub-block of the model: 1024 bits of frame `fr`, sub-block k, into out[128] */
+/* one sub-block of the model: 1024 bits of frame `fr`, sub-block k, into out[128]; the decoder's own bits d into dbits[128] as
+ * well (they are `out` unless diff: then out holds d[t] xor d[t - 1], and 0 stands for the bit before step 0) */
 void
-model_sub_block(const int8_t *soft, uint64_t m, const mdemod_frame_info &fr, int k, uint8_t *out)
+model_sub_block(const int8_t *soft, uint64_t m, const mdemod_frame_info &fr, int k, bool diff, uint8_t *out, uint8_t *dbits)
 {
-	const FrHyp y = fr_hyp(fr.hypothesis);
 	const uint64_t s = fr.position + static_cast<uint64_t>(FR_SUB) * k;
 	const uint64_t lo = s >= FR_HALO ? s - FR_HALO : 0, hi = std::min<uint64_t>(m, s + FR_SUB + FR_HALO);
 	const uint32_t T = static_cast<uint32_t>(hi - lo), off = static_cast<uint32_t>(s - lo);
@@ -59,7 +51,7 @@ model_sub_block(const int8_t *soft, uint64_t m, const mdemod_frame_info &fr, int
 	for (int i = 0; i < 64; i++) pm[i] = 0;
 	for (uint32_t t = 0; t < T; t++) {
 		int ip, qp;
-		through(soft, lo + t, y, ip, qp);
+		through(soft, m, lo + t, fr.hypothesis, ip, qp);
 		uint64_t word = 0;
 		for (uint32_t ns = 0; ns < 64; ns++) {
 			const uint32_t bit = ns & 1u, p0 = ns >> 1, p1 = (ns >> 1) | 32u;
@@ -77,10 +69,12 @@ model_sub_block(const int8_t *soft, uint64_t m, const mdemod_frame_info &fr, int
 	for (uint32_t i = 1; i < 64; i++)
 		if (pm[i] > pm[state]) state = i;                                 /* ties: the lowest state */
 	memset(out, 0, FR_SUB / 8);
+	memset(dbits, 0, FR_SUB / 8);
 	for (uint32_t t = T; t-- > 0;) {
-		if (t >= off && t < off + FR_SUB && (state & 1u)) {
-			const uint32_t j = t - off;
-			out[j >> 3] |= static_cast<uint8_t>(0x80u >> (j & 7u));
+		if (t >= off && t < off + FR_SUB) {
+			const uint32_t j = t - off, d = state & 1u, before = t ? (state >> 1) & 1u : 0u;   /* (bit 1 of the state: the bit of step t - 1) */
+			if (d) dbits[j >> 3] |= static_cast<uint8_t>(0x80u >> (j & 7u));
+			if (diff ? d ^ before : d) out[j >> 3] |= static_cast<uint8_t>(0x80u >> (j & 7u));
 		}
 		const uint32_t d = static_cast<uint32_t>(dec[t] >> state) & 1u;
 		state = (state >> 1) | (d << 5);
@@ -88,15 +82,14 @@ model_sub_block(const int8_t *soft, uint64_t m, const mdemod_frame_info &fr, int
 }
 
 uint32_t
-model_channel_errors(const int8_t *soft, const mdemod_frame_info &fr, const uint8_t *cadu)
+model_channel_errors(const int8_t *soft, uint64_t m, const mdemod_frame_info &fr, const uint8_t *cadu)
 {
-	const FrHyp y = fr_hyp(fr.hypothesis);
 	uint32_t reg = 0, errors = 0;
 	for (uint32_t n = 0; n < FR_FRAME; n++) {
 		reg = enc_step(reg, (cadu[n >> 3] >> (7 - (n & 7u))) & 1u);
 		if (n < FR_LEAD) continue;
 		int ip, qp;
-		through(soft, fr.position + n, y, ip, qp);
+		through(soft, m, fr.position + n, fr.hypothesis, ip, qp);
 		errors += (ip > 0) != (enc_c1(reg) > 0);
 		errors += (qp > 0) != (enc_c2(reg) > 0);
 	}
@@ -112,6 +105,99 @@ fr_pattern(int8_t a[FR_TAPS], int8_t b[FR_TAPS])
 	int8_t sym[64];
 	(void)mdemod_frames_model_encode(marker, 4, 0, sym);
 	for (int k = 0; k < FR_TAPS; k++) { a[k] = sym[2 * (FR_LEAD + k)]; b[k] = sym[2 * (FR_LEAD + k) + 1]; }
+}
+
+void
+fr_pattern_diff(int8_t a[FR_TAPS], int8_t b[FR_TAPS])
+{
+	static const uint8_t marker[4] = { 0x1A, 0xCF, 0xFC, 0x1D };
+	uint8_t coded[4] = { 0, 0, 0, 0 };
+	uint32_t d = 0;                                                          /* d[-1] */
+	for (int t = 0; t < 32; t++) {
+		d ^= (marker[t >> 3] >> (7 - (t & 7))) & 1u;
+		coded[t >> 3] |= static_cast<uint8_t>(d << (7 - (t & 7)));
+	}
+	int8_t sym[64];
+	(void)mdemod_frames_model_encode(coded, 4, 0, sym);
+	for (int k = 0; k < FR_TAPS; k++) { a[k] = sym[2 * (FR_LEAD + k)]; b[k] = sym[2 * (FR_LEAD + k) + 1]; }
+}
+
+int
+fr_mode_of(const mdemod_frames_link *link, FrMode &md)
+{
+	md.diff = md.skew = false;
+	if (!link) return MDEMOD_OK;
+	if (link->differential > 1 || link->skew > 1) REFUSE("frames: link switches are 0 or 1 (differential %u, skew %u)", link->differential, link->skew);
+	if (link->reserved[0] || link->reserved[1]) REFUSE("frames: the reserved words of mdemod_frames_link must be 0");
+	md.diff = link->differential != 0;
+	md.skew = link->skew != 0;
+	return MDEMOD_OK;
+}
+
+int
+fr_check_frames(const mdemod_frame_info *frames, uint64_t n_frames, uint64_t m, FrMode md)
+{
+	for (uint64_t f = 0; f < n_frames; f++) {
+		if (frames[f].hypothesis >= fr_mode_hyps(md))
+			REFUSE("frames: frame %llu has hypothesis %u (0..%u)", (unsigned long long)f, frames[f].hypothesis, fr_mode_hyps(md) - 1);
+		if (!fr_mode_allows(frames[f].hypothesis, md))
+			REFUSE("frames: frame %llu has hypothesis %u, which is outside the differential set (h in 0, 1, 4, 5)", (unsigned long long)f, frames[f].hypothesis);
+		if (frames[f].position > m || m - frames[f].position < FR_FRAME)
+			REFUSE("frames: frame %llu at symbol %llu is not complete in a stream of %llu symbols", (unsigned long long)f,
+			       (unsigned long long)frames[f].position, (unsigned long long)m);
+	}
+	return MDEMOD_OK;
+}
+
+int
+fr_check_candidates(const mdemod_frames_candidate *cand, uint64_t n_windows, uint64_t m, FrMode md)
+{
+	if (n_windows != fr_mode_windows(m, md))
+		REFUSE("frames: %llu candidates for a stream of %llu symbols, which has %llu windows", (unsigned long long)n_windows,
+		       (unsigned long long)m, (unsigned long long)fr_mode_windows(m, md));
+	for (uint64_t w = 0; w < n_windows; w++) {
+		if (cand[w].hypothesis >= fr_mode_hyps(md))
+			REFUSE("frames: candidate %llu has hypothesis %u (0..%u)", (unsigned long long)w, cand[w].hypothesis, fr_mode_hyps(md) - 1);
+		if (!fr_mode_allows(cand[w].hypothesis, md))
+			REFUSE("frames: candidate %llu has hypothesis %u, which is outside the differential set (h in 0, 1, 4, 5)", (unsigned long long)w, cand[w].hypothesis);
+		if (cand[w].position / FR_FRAME != w || cand[w].position >= m - fr_mode_span(md))
+			REFUSE("frames: candidate %llu at symbol %llu is outside its window", (unsigned long long)w, (unsigned long long)cand[w].position);
+	}
+	return MDEMOD_OK;
+}
+
+/* the candidates under a mode, as the specification words them: every allowed H of every position, the symbols taken through H */
+void
+fr_model_candidates(const int8_t *soft, uint64_t m, FrMode md, mdemod_frames_candidate *cand)
+{
+	const uint64_t n_windows = fr_mode_windows(m, md), span = fr_mode_span(md);
+	int8_t a[FR_TAPS], b[FR_TAPS];
+	if (md.diff) fr_pattern_diff(a, b); else fr_pattern(a, b);
+	for (uint64_t w = 0; w < n_windows; w++) {
+		const uint64_t first = w * FR_FRAME, end = std::min<uint64_t>(first + FR_FRAME, m - span);
+		mdemod_frames_candidate best = { first, INT32_MIN, 0 };
+		for (uint64_t p = first; p < end; p++)
+			for (uint32_t H = 0; H < fr_mode_hyps(md); H++) {
+				if (!fr_mode_allows(H, md)) continue;
+				int32_t score = 0;
+				for (int k = 0; k < FR_TAPS; k++) {
+					int ip, qp;
+					through(soft, m, p + FR_LEAD + k, H, ip, qp);
+					score += ip * a[k] + qp * b[k];
+				}
+				if (md.diff && score < 0) score = -score;                      /* polarity is only a sign */
+				if (score > best.score) { best.position = p; best.score = score; best.hypothesis = H; }   /* ascending p, H: the first of equals stays */
+			}
+		cand[w] = best;
+	}
+}
+
+void
+fr_model_frame(const int8_t *soft, uint64_t m, FrMode md, mdemod_frame_info &frame, uint8_t *cadu)
+{
+	uint8_t dbits[MDEMOD_FRAME_BYTES];
+	for (int k = 0; k < 8; k++) model_sub_block(soft, m, frame, k, md.diff, cadu + k * (FR_SUB / 8), dbits + k * (FR_SUB / 8));
+	frame.channel_errors = model_channel_errors(soft, m, frame, dbits);      /* counted on d, before the xor */
 }
 
 int
@@ -200,14 +286,8 @@ try { MDEMOD_API_ENTER
 	mdemod_frames_opts o;
 	const int rc = fr_settings(opts, o);
 	if (rc) return rc;
-	if (n_windows != mdemod_frames_windows(m))
-		REFUSE("frames: %llu candidates for a stream of %llu symbols, which has %llu windows", (unsigned long long)n_windows,
-		       (unsigned long long)m, (unsigned long long)mdemod_frames_windows(m));
-	for (uint64_t w = 0; w < n_windows; w++) {
-		if (cand[w].hypothesis > 7) REFUSE("frames: candidate %llu has hypothesis %u (0..7)", (unsigned long long)w, cand[w].hypothesis);
-		if (cand[w].position / FR_FRAME != w || cand[w].position >= m - FR_SPAN)
-			REFUSE("frames: candidate %llu at symbol %llu is outside its window", (unsigned long long)w, (unsigned long long)cand[w].position);
-	}
+	const int bad = fr_check_candidates(cand, n_windows, m, FrMode{ false, false });
+	if (bad) return bad;
 	std::vector<mdemod_frame_info> found;
 	(void)fr_track(o, cand, n_windows, m, found);
 	*n_frames = found.size();
@@ -265,13 +345,9 @@ int
 mdemod_frames_model_viterbi(const int8_t *soft, uint64_t m, mdemod_frame_info *frames, uint64_t n_frames, uint8_t *cadu)
 try { MDEMOD_API_ENTER
 	if (n_frames && (!soft || !frames || !cadu)) REFUSE("mdemod_frames_model_viterbi: the symbols, the frames and the output are needed");
-	const int rc = check_frames(frames, n_frames, m);
+	const int rc = fr_check_frames(frames, n_frames, m, FrMode{ false, false });
 	if (rc) return rc;
-	for (uint64_t f = 0; f < n_frames; f++) {
-		uint8_t *out = cadu + f * MDEMOD_FRAME_BYTES;
-		for (int k = 0; k < 8; k++) model_sub_block(soft, m, frames[f], k, out + k * (FR_SUB / 8));
-		frames[f].channel_errors = model_channel_errors(soft, frames[f], out);
-	}
+	for (uint64_t f = 0; f < n_frames; f++) fr_model_frame(soft, m, FrMode{ false, false }, frames[f], cadu + f * MDEMOD_FRAME_BYTES);
 	return MDEMOD_OK;
 } MDEMOD_API_CATCH
 

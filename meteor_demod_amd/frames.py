@@ -4,6 +4,11 @@
 GPU), ``decode`` all three steps (a device tensor of soft symbols, or a numpy array, which is copied in pieces), ``decode_file``
 a ``.s`` file to CADU bytes plus a report.  ``model_*`` is the host model of csrc/frames_host.cpp, the kernels' specification.
 This module keeps its own binding table, as ``survey.py`` does.
+
+The link variant (include/meteor_demod_amd_frames_link.h: Meteor-M N2-3 / N2-4) is chosen by two keywords on ``candidates``,
+``track``, ``viterbi``, ``decode``, ``decode_file`` and ``model_*``: ``differential=True`` for an NRZ-M coded sender, ``skew=True``
+to let the rails stand one symbol apart (OQPSK).  ``hypothesis`` then carries H = h + 8 s.  With both off (the default) the plain
+entries are called.
 """
 from __future__ import annotations
 
@@ -31,6 +36,10 @@ class MdemodFrameInfo(C.Structure):
                 ("channel_errors", C.c_uint32), ("run", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class MdemodFramesLink(C.Structure):
+    _fields_ = [("differential", C.c_uint32), ("skew", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 _P = C.POINTER
 # name -> (restype, argtypes): every entry of include/meteor_demod_amd_frames.h
 SIGNATURES = {
@@ -55,6 +64,27 @@ MODEL_SIGNATURES = {
                                              _P(C.c_uint64)]),
 }
 
+# every entry of include/meteor_demod_amd_frames_link.h
+LINK_SIGNATURES = {
+    "mdemod_frames_link_windows": (C.c_uint64, [_P(MdemodFramesLink), C.c_uint64]),
+    "mdemod_frames_link_candidates_device": (C.c_int, [_P(MdemodFramesLink), C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]),
+    "mdemod_frames_link_track": (C.c_int, [_P(MdemodFramesLink), _P(MdemodFramesOpts), _P(MdemodFramesCandidate), C.c_uint64, C.c_uint64,
+                                           _P(MdemodFrameInfo), C.c_uint64, _P(C.c_uint64)]),
+    "mdemod_frames_link_viterbi_device": (C.c_int, [_P(MdemodFramesLink), C.c_void_p, C.c_uint64, _P(MdemodFrameInfo), C.c_uint64, C.c_void_p, C.c_int,
+                                                    C.c_void_p]),
+    "mdemod_frames_link_decode_device": (C.c_int, [_P(MdemodFramesLink), _P(MdemodFramesOpts), C.c_void_p, C.c_uint64, C.c_void_p, _P(MdemodFrameInfo),
+                                                   C.c_uint64, _P(C.c_uint64), C.c_int, C.c_void_p]),
+    "mdemod_frames_link_decode_host": (C.c_int, [_P(MdemodFramesLink), _P(MdemodFramesOpts), C.c_void_p, C.c_uint64, C.c_void_p, _P(MdemodFrameInfo),
+                                                 C.c_uint64, _P(C.c_uint64), C.c_int]),
+}
+LINK_MODEL_SIGNATURES = {
+    "mdemod_frames_model_link_pattern": (None, [_P(MdemodFramesLink), C.c_void_p, C.c_void_p]),
+    "mdemod_frames_model_link_candidates": (C.c_int, [_P(MdemodFramesLink), C.c_void_p, C.c_uint64, _P(MdemodFramesCandidate)]),
+    "mdemod_frames_model_link_viterbi": (C.c_int, [_P(MdemodFramesLink), C.c_void_p, C.c_uint64, _P(MdemodFrameInfo), C.c_uint64, C.c_void_p]),
+    "mdemod_frames_model_link_decode": (C.c_int, [_P(MdemodFramesLink), _P(MdemodFramesOpts), C.c_void_p, C.c_uint64, C.c_void_p, _P(MdemodFrameInfo),
+                                                  C.c_uint64, _P(C.c_uint64)]),
+}
+
 _lib = None
 
 
@@ -63,7 +93,7 @@ def lib() -> C.CDLL:
     global _lib
     if _lib is None:
         h = _capi.lib()
-        for name, (res, args) in {**SIGNATURES, **MODEL_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **MODEL_SIGNATURES, **LINK_SIGNATURES, **LINK_MODEL_SIGNATURES}.items():
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args
@@ -117,8 +147,21 @@ def make_opts(**opts) -> MdemodFramesOpts:
     return o
 
 
-def windows(m: int) -> int:
-    return int(lib().mdemod_frames_windows(int(m)))
+def make_link(differential=False, skew=False):
+    """The ``mdemod_frames_link`` of the two keywords, or None when both are off (the plain entries are called then)."""
+    for name, v in (("differential", differential), ("skew", skew)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise TypeError(f"frames: {name} is a switch (True or False), got {v!r}")
+    if not differential and not skew:
+        return None
+    link = MdemodFramesLink()
+    link.differential, link.skew = int(differential), int(skew)
+    return link
+
+
+def windows(m: int, *, skew=False) -> int:
+    link = make_link(False, skew)
+    return int(lib().mdemod_frames_link_windows(C.byref(link), int(m)) if link else lib().mdemod_frames_windows(int(m)))
 
 
 def _frames(arr, n) -> list[Frame]:
@@ -159,67 +202,92 @@ def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-def candidates_tensor(soft):
-    """``mdemod_frames_candidates_device`` as it writes: an int32 [windows, 4] device tensor (position low, position high, score,
-    hypothesis), queued on the current stream."""
+def candidates_tensor(soft, *, differential=False, skew=False):
+    """``mdemod_frames_candidates_device`` (``mdemod_frames_link_candidates_device`` with a switch on) as it writes: an int32
+    [windows, 4] device tensor (position low, position high, score, hypothesis), queued on the current stream."""
     import torch
+    link = make_link(differential, skew)
     _check_soft(soft)
     dev = soft.device.index or 0
     m = int(soft.shape[0])
-    out = torch.zeros((windows(m), 4), dtype=torch.int32, device=soft.device)
-    check(lib().mdemod_frames_candidates_device(C.c_void_p(soft.data_ptr()), m, C.c_void_p(out.data_ptr()), dev, _stream(dev)),
-          "mdemod_frames_candidates_device")
+    out = torch.zeros((windows(m, skew=skew), 4), dtype=torch.int32, device=soft.device)
+    if link is None:
+        check(lib().mdemod_frames_candidates_device(C.c_void_p(soft.data_ptr()), m, C.c_void_p(out.data_ptr()), dev, _stream(dev)),
+              "mdemod_frames_candidates_device")
+    else:
+        check(lib().mdemod_frames_link_candidates_device(C.byref(link), C.c_void_p(soft.data_ptr()), m, C.c_void_p(out.data_ptr()), dev, _stream(dev)),
+              "mdemod_frames_link_candidates_device")
     return out
 
 
-def candidates(soft) -> list[Candidate]:
+def candidates(soft, *, differential=False, skew=False) -> list[Candidate]:
     """One candidate per window of ``soft`` (int8 [m, 2] device tensor)."""
-    a = candidates_tensor(soft).cpu().numpy().astype(np.int64)
+    a = candidates_tensor(soft, differential=differential, skew=skew).cpu().numpy().astype(np.int64)
     return [Candidate(int((r[0] & 0xFFFFFFFF) | (r[1] << 32)), int(r[3]), int(r[2])) for r in a]
 
 
-def track(cands: list[Candidate], m: int, **opts) -> list[Frame]:
+def track(cands: list[Candidate], m: int, *, differential=False, skew=False, **opts) -> list[Frame]:
     """``mdemod_frames_track`` (no GPU): the frame list of a stream of ``m`` symbols.  Options: ``min_run``, ``flywheel``."""
+    link = make_link(differential, skew)
     o = make_opts(**opts)
     cap = max(1, int(m) // FRAME_SYMBOLS)
     out = (MdemodFrameInfo * cap)()
     n = C.c_uint64()
-    check(lib().mdemod_frames_track(C.byref(o), _cands_to_c(cands), len(cands), int(m), out, cap, C.byref(n)), "mdemod_frames_track")
+    if link is None:
+        check(lib().mdemod_frames_track(C.byref(o), _cands_to_c(cands), len(cands), int(m), out, cap, C.byref(n)), "mdemod_frames_track")
+    else:
+        check(lib().mdemod_frames_link_track(C.byref(link), C.byref(o), _cands_to_c(cands), len(cands), int(m), out, cap, C.byref(n)),
+              "mdemod_frames_link_track")
     return _frames(out, min(n.value, cap))
 
 
-def viterbi(soft, frames: list[Frame]):
+def viterbi(soft, frames: list[Frame], *, differential=False, skew=False):
     """``mdemod_frames_viterbi_device``: (uint8 [n, 1024] device tensor, the frames with ``channel_errors``)."""
     import torch
+    link = make_link(differential, skew)
     _check_soft(soft)
     dev = soft.device.index or 0
     arr = _to_c(frames)
     out = torch.zeros((len(frames), FRAME_BYTES), dtype=torch.uint8, device=soft.device)
-    check(lib().mdemod_frames_viterbi_device(C.c_void_p(soft.data_ptr()), int(soft.shape[0]), arr, len(frames), C.c_void_p(out.data_ptr()), dev,
-                                             _stream(dev)), "mdemod_frames_viterbi_device")
+    if link is None:
+        check(lib().mdemod_frames_viterbi_device(C.c_void_p(soft.data_ptr()), int(soft.shape[0]), arr, len(frames), C.c_void_p(out.data_ptr()), dev,
+                                                 _stream(dev)), "mdemod_frames_viterbi_device")
+    else:
+        check(lib().mdemod_frames_link_viterbi_device(C.byref(link), C.c_void_p(soft.data_ptr()), int(soft.shape[0]), arr, len(frames),
+                                                      C.c_void_p(out.data_ptr()), dev, _stream(dev)), "mdemod_frames_link_viterbi_device")
     return out, _frames(arr, len(frames))
 
 
 def decode(soft, **opts):
     """Sync search, tracker and Viterbi: (uint8 [n, 1024] numpy array of CADUs, list of ``Frame``).  ``soft`` is an int8 [m, 2]
     device tensor (``mdemod_frames_decode_device``) or a numpy array (``mdemod_frames_decode_host``, copied in pieces of
-    ``piece_symbols``).  Options: the fields of ``mdemod_frames_opts``; ``device`` for a numpy array."""
+    ``piece_symbols``).  Options: the fields of ``mdemod_frames_opts``; ``device`` for a numpy array; ``differential`` and ``skew``
+    (the link variant: ``mdemod_frames_link_decode_*``)."""
     device = int(opts.pop("device", 0))
+    link = make_link(opts.pop("differential", False), opts.pop("skew", False))
     o = make_opts(**opts)
     n = C.c_uint64()
     if isinstance(soft, np.ndarray):
         a = _host_soft(soft)
         cap = max(1, a.shape[0] // FRAME_SYMBOLS)
         out, cadu = (MdemodFrameInfo * cap)(), np.zeros((cap, FRAME_BYTES), dtype=np.uint8)
-        check(lib().mdemod_frames_decode_host(C.byref(o), a.ctypes.data, a.shape[0], cadu.ctypes.data, out, cap, C.byref(n), device),
-              "mdemod_frames_decode_host")
+        if link is None:
+            check(lib().mdemod_frames_decode_host(C.byref(o), a.ctypes.data, a.shape[0], cadu.ctypes.data, out, cap, C.byref(n), device),
+                  "mdemod_frames_decode_host")
+        else:
+            check(lib().mdemod_frames_link_decode_host(C.byref(link), C.byref(o), a.ctypes.data, a.shape[0], cadu.ctypes.data, out, cap, C.byref(n),
+                                                       device), "mdemod_frames_link_decode_host")
     else:
         _check_soft(soft)
         dev = soft.device.index or 0
         cap = max(1, int(soft.shape[0]) // FRAME_SYMBOLS)
         out, cadu = (MdemodFrameInfo * cap)(), np.zeros((cap, FRAME_BYTES), dtype=np.uint8)
-        check(lib().mdemod_frames_decode_device(C.byref(o), C.c_void_p(soft.data_ptr()), int(soft.shape[0]), cadu.ctypes.data, out, cap, C.byref(n),
-                                                dev, _stream(dev)), "mdemod_frames_decode_device")
+        if link is None:
+            check(lib().mdemod_frames_decode_device(C.byref(o), C.c_void_p(soft.data_ptr()), int(soft.shape[0]), cadu.ctypes.data, out, cap,
+                                                    C.byref(n), dev, _stream(dev)), "mdemod_frames_decode_device")
+        else:
+            check(lib().mdemod_frames_link_decode_device(C.byref(link), C.byref(o), C.c_void_p(soft.data_ptr()), int(soft.shape[0]), cadu.ctypes.data,
+                                                         out, cap, C.byref(n), dev, _stream(dev)), "mdemod_frames_link_decode_device")
     k = min(n.value, cap)
     return cadu[:k].copy(), _frames(out, k)
 
@@ -247,34 +315,52 @@ def model_encode(data: bytes, reg: int = 0):
     return sym, int(reg)
 
 
-def model_pattern():
+def model_pattern(*, differential=False):
     a, b = np.zeros(26, dtype=np.int8), np.zeros(26, dtype=np.int8)
-    lib().mdemod_frames_model_pattern(a.ctypes.data, b.ctypes.data)
+    link = make_link(differential, False)
+    if link is None:
+        lib().mdemod_frames_model_pattern(a.ctypes.data, b.ctypes.data)
+    else:
+        lib().mdemod_frames_model_link_pattern(C.byref(link), a.ctypes.data, b.ctypes.data)
     return a, b
 
 
-def model_candidates(soft) -> list[Candidate]:
+def model_candidates(soft, *, differential=False, skew=False) -> list[Candidate]:
+    link = make_link(differential, skew)
     a = _host_soft(soft)
-    n = windows(a.shape[0])
+    n = windows(a.shape[0], skew=skew)
     out = (MdemodFramesCandidate * max(1, n))()
-    check(lib().mdemod_frames_model_candidates(a.ctypes.data, a.shape[0], out), "mdemod_frames_model_candidates")
+    if link is None:
+        check(lib().mdemod_frames_model_candidates(a.ctypes.data, a.shape[0], out), "mdemod_frames_model_candidates")
+    else:
+        check(lib().mdemod_frames_model_link_candidates(C.byref(link), a.ctypes.data, a.shape[0], out), "mdemod_frames_model_link_candidates")
     return [Candidate(int(c.position), int(c.hypothesis), int(c.score)) for c in out[:n]]
 
 
-def model_viterbi(soft, frames: list[Frame]):
+def model_viterbi(soft, frames: list[Frame], *, differential=False, skew=False):
+    link = make_link(differential, skew)
     a = _host_soft(soft)
     arr = _to_c(frames)
     cadu = np.zeros((len(frames), FRAME_BYTES), dtype=np.uint8)
-    check(lib().mdemod_frames_model_viterbi(a.ctypes.data, a.shape[0], arr, len(frames), cadu.ctypes.data), "mdemod_frames_model_viterbi")
+    if link is None:
+        check(lib().mdemod_frames_model_viterbi(a.ctypes.data, a.shape[0], arr, len(frames), cadu.ctypes.data), "mdemod_frames_model_viterbi")
+    else:
+        check(lib().mdemod_frames_model_link_viterbi(C.byref(link), a.ctypes.data, a.shape[0], arr, len(frames), cadu.ctypes.data),
+              "mdemod_frames_model_link_viterbi")
     return cadu, _frames(arr, len(frames))
 
 
 def model_decode(soft, **opts):
+    link = make_link(opts.pop("differential", False), opts.pop("skew", False))
     a = _host_soft(soft)
     o = make_opts(**opts)
     cap = max(1, a.shape[0] // FRAME_SYMBOLS)
     out, cadu = (MdemodFrameInfo * cap)(), np.zeros((cap, FRAME_BYTES), dtype=np.uint8)
     n = C.c_uint64()
-    check(lib().mdemod_frames_model_decode(C.byref(o), a.ctypes.data, a.shape[0], cadu.ctypes.data, out, cap, C.byref(n)), "mdemod_frames_model_decode")
+    if link is None:
+        check(lib().mdemod_frames_model_decode(C.byref(o), a.ctypes.data, a.shape[0], cadu.ctypes.data, out, cap, C.byref(n)), "mdemod_frames_model_decode")
+    else:
+        check(lib().mdemod_frames_model_link_decode(C.byref(link), C.byref(o), a.ctypes.data, a.shape[0], cadu.ctypes.data, out, cap, C.byref(n)),
+              "mdemod_frames_model_link_decode")
     k = min(n.value, cap)
     return cadu[:k].copy(), _frames(out, k)
