@@ -39,6 +39,10 @@
  * pass; the .cadu is written only when --cadu is given too.  Weak references; refused with --stdout.
  * --diff and --skew choose the link variant of the frame pass (include/meteor_demod_amd_frames_link.h: NRZ-M coding, a one-symbol
  * skew between the rails): what Meteor-M N2-3 / N2-4 need with -m oqpsk.  Only with --cadu / --vcdu.  Weak references.
+ * --int puts the 80 k interleaved mode (include/meteor_demod_amd_interleave.h) in front of the frame pass: the interleaver's sync
+ * word found, followed and stripped and the 36 branches undone on the GPU (branch delay --int-delay, 2048 by default), one more
+ * line on stdout.  Independent of --diff; --skew is accepted and ignored beside it, because the sync word resolves the skew.  Only
+ * with --cadu / --vcdu.  Weak references.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -60,6 +64,7 @@
 #include "meteor_demod_amd_frames.h"
 #include "meteor_demod_amd_frames_link.h"
 #include "meteor_demod_amd_rs.h"
+#include "meteor_demod_amd_interleave.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
 #endif
@@ -93,6 +98,7 @@ static const struct option longopts[] = {
 	{ "tui-selftest", 0, NULL, 0x08 }, { "tui", 0, NULL, 0x09 }, { "jobs", 1, NULL, 0x0a },
 	{ "offset", 1, NULL, 0x0b },    { "decimate", 1, NULL, 0x0c }, { "scan", 0, NULL, 0x0d },
 	{ "cadu", 0, NULL, 0x0e },      { "vcdu", 0, NULL, 0x0f },    { "diff", 0, NULL, 0x10 },    { "skew", 0, NULL, 0x11 },
+	{ "int", 0, NULL, 0x12 },       { "int-delay", 1, NULL, 0x13 },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -139,6 +145,18 @@ static int
 have_frames_link(void)
 {
 	return mdemod_frames_link_decode_host != NULL;
+}
+
+/* the 80 k interleaved mode (include/meteor_demod_amd_interleave.h: --int): weak as well */
+#pragma weak mdemod_il_default_opts
+#pragma weak mdemod_il_windows
+#pragma weak mdemod_il_max_output_symbols
+#pragma weak mdemod_il_decode_host
+
+static int
+have_interleave(void)
+{
+	return mdemod_il_default_opts && mdemod_il_windows && mdemod_il_max_output_symbols && mdemod_il_decode_host;
 }
 
 /* the transfer-frame layer's entries (include/meteor_demod_amd_rs.h: --vcdu): weak as well */
@@ -233,6 +251,11 @@ usage(const char *prog)
 	        "       --skew              With --cadu / --vcdu: the rails may stand one symbol apart, as after -m oqpsk when\n"
 	        "                           the carrier loop settles a quarter turn off; the frame pass tries both skews as well.\n"
 	        "                           Meteor-M N2-3 / N2-4 (72k OQPSK) want: -m oqpsk --skew --diff\n"
+	        "       --int               With --cadu / --vcdu: the 80k interleaved mode; the interleaver's sync word is found,\n"
+	        "                           followed across slips and stripped, and the stream deinterleaved on the GPU before\n"
+	        "                           the frame pass; one more line on stdout: segments, periods, mean sync score.\n"
+	        "                           --skew beside it is ignored (the sync word resolves the skew); --diff still applies\n"
+	        "       --int-delay <M>     The interleaver's branch delay (default: 2048)\n"
 	        "   -h, --help   -v, --version\n", prog);
 }
 
@@ -779,27 +802,48 @@ done:
 /* --cadu / --vcdu: the soft symbols of one finished output file through the frame layer, the CADUs (and the VCDUs) beside it.  0, or
  * the exit status. */
 static int
-cadu_file(const char *s_name, int device, int write_cadu, int write_vcdu, int diff, int skew)
+cadu_file(const char *s_name, int device, int write_cadu, int write_vcdu, int diff, int skew, uint32_t il_delay)
 {
 	FILE *f = fopen(s_name, "rb");
 	if (!f) { fprintf(stderr, "--cadu: %s: %s\n", s_name, strerror(errno)); return 1; }
 	long len = -1;
 	if (!fseek(f, 0, SEEK_END)) len = ftell(f);
 	if (len < 0 || fseek(f, 0, SEEK_SET)) { fprintf(stderr, "--cadu: cannot read %s\n", s_name); fclose(f); return 1; }
-	const uint64_t m = (uint64_t)len / 2, cap = m / MDEMOD_FRAME_SYMBOLS;
+	uint64_t m = (uint64_t)len / 2;
+	const uint64_t cap = m / MDEMOD_FRAME_SYMBOLS;
+	/* --int: the deinterleaved stream (never longer than this) and the segments (never more than the windows) */
+	const uint64_t il_room = il_delay ? mdemod_il_max_output_symbols(m) : 0, il_cap = il_delay ? mdemod_il_windows(m) : 0;
+	int8_t *deint = il_delay ? malloc((size_t)il_room * 2) : NULL;
+	mdemod_il_segment *segs = il_delay ? calloc(il_cap ? (size_t)il_cap : 1, sizeof(*segs)) : NULL;
 	int8_t *soft = malloc(len ? (size_t)len : 1);
 	uint8_t *cadu = malloc(cap ? (size_t)cap * MDEMOD_FRAME_BYTES : 1);
 	mdemod_frame_info *frames = calloc(cap ? (size_t)cap : 1, sizeof(*frames));
 	char *out_name = beside(s_name, ".cadu");
 	int code = 1;
-	if (!soft || !cadu || !frames || !out_name) { fprintf(stderr, "--cadu: out of memory reading %s\n", s_name); goto done; }
+	if (!soft || !cadu || !frames || !out_name || (il_delay && (!deint || !segs))) { fprintf(stderr, "--cadu: out of memory reading %s\n", s_name); goto done; }
 	if (fread(soft, 1, (size_t)len, f) != (size_t)len) { fprintf(stderr, "--cadu: cannot read %s\n", s_name); goto done; }
+	const int8_t *sym = soft;                                                    /* what the frame pass reads */
+	if (il_delay) {
+		mdemod_il_opts io;
+		mdemod_il_default_opts(&io);
+		io.branch_delay = il_delay;
+		uint64_t n_segs = 0, periods = 0;
+		int32_t mean = 0;
+		const int irc = mdemod_il_decode_host(&io, soft, m, deint, il_room, segs, il_cap, &n_segs, &periods, &mean, device);
+		if (irc != MDEMOD_OK) { fprintf(stderr, "--int: %s: %s\n", s_name, why_of(irc)); code = 2; goto done; }
+		printf("%s: interleaver: %llu segments, %llu periods, mean sync score %d / 24576\n", s_name, (unsigned long long)n_segs,
+		       (unsigned long long)periods, (int)mean);
+		const uint64_t written = periods < il_room / MDEMOD_IL_BRANCHES ? periods : il_room / MDEMOD_IL_BRANCHES;
+		sym = deint;
+		m = written * MDEMOD_IL_BRANCHES;
+		skew = 0;                                                                /* (resolved by the sync word) */
+	}
 	mdemod_frames_opts fo;
 	mdemod_frames_default_opts(&fo);
 	uint64_t n = 0;
 	mdemod_frames_link link = { (uint32_t)diff, (uint32_t)skew, { 0, 0 } };
-	const int rc = diff || skew ? mdemod_frames_link_decode_host(&link, &fo, soft, m, cadu, frames, cap, &n, device)
-	                            : mdemod_frames_decode_host(&fo, soft, m, cadu, frames, cap, &n, device);
+	const int rc = diff || skew ? mdemod_frames_link_decode_host(&link, &fo, sym, m, cadu, frames, cap, &n, device)
+	                            : mdemod_frames_decode_host(&fo, sym, m, cadu, frames, cap, &n, device);
 	if (rc != MDEMOD_OK) { fprintf(stderr, "--cadu: %s: %s\n", s_name, why_of(rc)); code = 2; goto done; }
 	if (n > cap) n = cap;
 	if (!write_cadu) { code = vcdu_file(s_name, cadu, n, device); goto done; }
@@ -818,7 +862,7 @@ cadu_file(const char *s_name, int device, int write_cadu, int write_vcdu, int di
 	       n ? (double)errors / (double)n : 0.0, MDEMOD_FRAME_DECISIONS);
 	code = write_vcdu ? vcdu_file(s_name, cadu, n, device) : 0;
 done:
-	free(out_name); free(frames); free(cadu); free(soft);
+	free(out_name); free(frames); free(cadu); free(soft); free(segs); free(deint);
 	fclose(f);
 	return code;
 }
@@ -834,7 +878,8 @@ main(int argc, char **argv)
 	int devs[MAX_DEVICES], n_dev = 0, plan = 0, jobs = 4;
 	int use_fe = 0, decimation = 1;
 	double offset_hz = 0.0;
-	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0, want_vcdu = 0, want_diff = 0, want_skew = 0;
+	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0, want_vcdu = 0, want_diff = 0, want_skew = 0, want_int = 0;
+	long int_delay = MDEMOD_IL_DEFAULT_BRANCH_DELAY;
 	double *auto_offsets = NULL;               /* --offset auto: the offset chosen for each file */
 #ifdef MDEMOD_TUI
 	int force_tui = 0;
@@ -861,6 +906,8 @@ main(int argc, char **argv)
 		case 0x0f: want_vcdu = 1; break;
 		case 0x10: want_diff = 1; break;
 		case 0x11: want_skew = 1; break;
+		case 0x12: want_int = 1; break;
+		case 0x13: int_delay = atol(optarg); break;
 		case 0x0b:
 			if (!strcmp(optarg, "auto")) { auto_offset = 1; use_fe = 1; break; }
 			auto_offset = 0;
@@ -947,6 +994,26 @@ main(int argc, char **argv)
 	if ((want_diff || want_skew) && !(want_cadu || want_vcdu)) {
 		fprintf(stderr, "--diff / --skew: only with --cadu or --vcdu (they change how the frames are found and decoded, not the soft symbols)\n");
 		return 1;
+	}
+	if (want_int && stdout_mode) {
+		fprintf(stderr, "--int: not with --stdout (the frames are decoded from the finished output file)\n");
+		return 1;
+	}
+	if (want_int && !(want_cadu || want_vcdu)) {
+		fprintf(stderr, "--int: only with --cadu or --vcdu (it changes how the frames are found and decoded, not the soft symbols)\n");
+		return 1;
+	}
+	if (want_int && !have_interleave()) {
+		fprintf(stderr, "--int: this library has no interleaved mode (built without include/meteor_demod_amd_interleave.h's entries)\n");
+		return 1;
+	}
+	if (want_int && (int_delay < 1 || int_delay > 0x7FFFFFFFL)) {
+		fprintf(stderr, "--int-delay: the branch delay is a number of bits, 1 or more\n");
+		return 1;
+	}
+	if (want_int && want_skew) {
+		fprintf(stderr, "--skew: ignored with --int (the interleaver's sync word resolves the skew)\n");
+		want_skew = 0;
 	}
 	if ((want_diff || want_skew) && !have_frames_link()) {
 		fprintf(stderr, "--diff / --skew: this library has no link variant of the frame layer (built without include/meteor_demod_amd_frames_link.h's entries)\n");
@@ -1150,6 +1217,6 @@ main(int argc, char **argv)
 	/* (the workers closed their files through their own copies of the stream_io entries: nothing of the originals is open any more) */
 	for (int i = 0; i < n_files; i++) { io[i].in = NULL; io[i].out = NULL; }
 	if ((want_cadu || want_vcdu) && rc_all == 0)
-		for (int i = 0; i < n_files && rc_all == 0; i++) rc_all = cadu_file(io[i].out_name, devs[i % n_dev], want_cadu, want_vcdu, want_diff, want_skew);
+		for (int i = 0; i < n_files && rc_all == 0; i++) rc_all = cadu_file(io[i].out_name, devs[i % n_dev], want_cadu, want_vcdu, want_diff, want_skew, want_int ? (uint32_t)int_delay : 0);
 	LEAVE(rc_all);
 }

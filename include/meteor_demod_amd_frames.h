@@ -6,7 +6,8 @@
  * code without GPU) and decodes them (Viterbi, GPU), and says for every frame how many channel bits the decoder corrected.
  * The entries below are QPSK framing.  Differential coding and a one-symbol skew between the rails (OQPSK at odd rotations: Meteor-M
  * N2-3 / N2-4) are the "link variant" specified at the end of this block; its entries are in include/meteor_demod_amd_frames_link.h.
- * NOT here: the 80 k interleaved mode.  Derandomising and Reed-Solomon follow in include/meteor_demod_amd_rs.h.
+ * The 80 k interleaved mode goes in front of this layer: include/meteor_demod_amd_interleave.h turns its raw symbols into a stream
+ * these entries take.  Derandomising and Reed-Solomon follow in include/meteor_demod_amd_rs.h.
  * The specification of the kernels is a host model (csrc/frames_host.cpp, exported as mdemod_frames_model_*, csrc/frames_host.h):
  * everything is integer arithmetic, and GPU bytes equal model bytes.
  *

@@ -13,7 +13,8 @@ from . import frames  # noqa: F401
 from .frames import Frame  # noqa: F401
 from . import rs  # noqa: F401
 from .rs import RsInfo  # noqa: F401
+from . import interleave  # noqa: F401
 
 __all__ = ["DemodConfig", "Demodulator", "derive_tables", "scale_freq_max",
            "FrontEnd", "FrontEndConfig", "demodulate_recording_frontend", "design_taps",
-           "survey", "Hit", "survey_plan", "frames", "Frame", "rs", "RsInfo"]
+           "survey", "Hit", "survey_plan", "frames", "Frame", "rs", "RsInfo", "interleave"]

@@ -258,12 +258,29 @@ def viterbi(soft, frames: list[Frame], *, differential=False, skew=False):
     return out, _frames(arr, len(frames))
 
 
+def _deinterleaved(soft, opts: dict, device: int = 0):
+    """Takes ``interleaved`` and ``branch_delay`` out of ``opts``.  With ``interleaved`` the stream goes through
+    ``interleave.decode`` on the device first and ``skew`` is switched off (the interleaver's sync word has resolved it); without,
+    ``soft`` comes back as it is."""
+    interleaved, branch_delay = opts.pop("interleaved", False), opts.pop("branch_delay", 2048)
+    if not isinstance(interleaved, (bool, np.bool_)):
+        raise TypeError(f"frames: interleaved is a switch (True or False), got {interleaved!r}")
+    if not interleaved:
+        return soft
+    from . import interleave
+    opts["skew"] = False
+    kw = dict(device=device) if isinstance(soft, np.ndarray) else {}
+    return interleave.decode(soft, branch_delay=branch_delay, **kw)[0]
+
+
 def decode(soft, **opts):
     """Sync search, tracker and Viterbi: (uint8 [n, 1024] numpy array of CADUs, list of ``Frame``).  ``soft`` is an int8 [m, 2]
     device tensor (``mdemod_frames_decode_device``) or a numpy array (``mdemod_frames_decode_host``, copied in pieces of
     ``piece_symbols``).  Options: the fields of ``mdemod_frames_opts``; ``device`` for a numpy array; ``differential`` and ``skew``
-    (the link variant: ``mdemod_frames_link_decode_*``)."""
+    (the link variant: ``mdemod_frames_link_decode_*``); ``interleaved`` and ``branch_delay`` (the 80 k interleaved mode: the stream
+    is deinterleaved on the device first, ``interleave.decode``, and the frame pass runs with ``skew`` off)."""
     device = int(opts.pop("device", 0))
+    soft = _deinterleaved(soft, opts, device)
     link = make_link(opts.pop("differential", False), opts.pop("skew", False))
     o = make_opts(**opts)
     n = C.c_uint64()

@@ -187,8 +187,10 @@ def soft_to_vcdu(soft, **opts):
     """Soft symbols (int8 [m, 2] device tensor) to (VCDUs [n, 892] device tensor, report [n, 8] device tensor, the frame list):
     ``frames.candidates`` -> ``frames.track`` -> ``frames.viterbi`` -> ``decode``; the symbols, the CADUs and the VCDUs stay on the
     device.  Options: ``min_run`` and ``flywheel`` go to the tracker, ``differential`` and ``skew`` (the link variant of the frame
-    layer: Meteor-M N2-3 / N2-4) to all three frame steps, the rest to ``decode``."""
+    layer: Meteor-M N2-3 / N2-4) to all three frame steps, the rest to ``decode``.  ``interleaved`` and ``branch_delay`` (the 80 k
+    interleaved mode): the stream is deinterleaved on the device first (``interleave.decode``), and ``skew`` is off after that."""
     from . import frames
+    soft = frames._deinterleaved(soft, opts)
     track_opts = {k: opts.pop(k) for k in ("min_run", "flywheel") if k in opts}
     link = {k: opts.pop(k) for k in ("differential", "skew") if k in opts}
     found = frames.track(frames.candidates(soft, **link), int(soft.shape[0]), **link, **track_opts)
