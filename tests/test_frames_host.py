@@ -1,5 +1,6 @@
 """CPU tests of the frame layer (include/meteor_demod_amd_frames.h): the code's conventions against the known marker words, the
-host model (csrc/frames_host.cpp) against transmitted data it must recover, the tracker's cases, a recording through the CPU
+host model (csrc/frames_host.cpp) against transmitted data it must recover, its decoder against an independent full-stream
+maximum-likelihood reference (tests/viterbi_ref.py) where it errs, the tracker's cases, a recording through the CPU
 demodulator and the model, the exports and guards of the new entries, the C host linked without them, and a sanitizer fuzz of the
 tracker and the model.  No GPU is touched."""
 from __future__ import annotations
@@ -94,6 +95,99 @@ def test_minus_128_is_negated_in_int32():
     a, b = frames.model_pattern()
     want = int(np.where(a > 0, 128, 127).sum() + np.where(b > 0, 128, 127).sum())      # a coded 1: -(-128) = 128; a coded 0: -(127) times -1
     assert [f.score for f in fr] == [want] * 3
+
+
+# ------------------------------------------------------------------------------------------- the decoder is maximum-likelihood
+# viterbi_ref.ml_stream: two frames that tile a stream of 16 384 symbols, sent through the inverse of h with receive seed 400 + h at
+# 2 dB and 500 + h at 3 dB.  Measured for these seeds (h = 0..7; bits of the full-stream ML decoding that differ from what was sent,
+# of 16 384): 139 117 47 25 81 67 61 45 at 2 dB, 2 0 13 0 0 7 25 3 at 3 dB; windowed rule against full-stream decoding: 0 differing
+# bits in all sixteen (no seed had to be replaced).
+ML_CASES = [(h, esn0) for esn0 in (2.0, 3.0) for h in range(8)]
+
+
+def _ml_errors(st, bits, esn0):
+    """The premise of a 2 dB case: the ML decoder itself errs, at least 10 times over the stream."""
+    errors = int((bits != st.bits).sum())
+    assert esn0 != 2.0 or errors >= 10, errors
+    return errors
+
+
+@pytest.mark.parametrize("h,esn0", ML_CASES)
+def test_reference_windowed_rule_equals_full_stream_decoding(h, esn0):
+    """viterbi_ref itself: the header's sub-block rule in numpy (ml_decode on each [s - 128, s + 1152) clamped to the stream, the
+    middle 1024 bits kept) gives the bits of one ml_decode over the whole stream, and those bits reach M*."""
+    import viterbi_ref as V
+    st, _, sym, d, best = V.ml_case(False, h, esn0)
+    assert len(sym) == 2 * FRAME and st.positions == [0, FRAME]
+    windowed = np.concatenate([V.windowed_decode(sym, p)[0] for p in st.positions])
+    differing = int((windowed != d).sum())
+    print(f"h {h}, {esn0} dB: {_ml_errors(st, d, esn0)} of {len(d)} bits of the ML decoding differ from what was sent; windowed != full-stream in "
+          f"{differing}; M* {best}, metric of the decoded path {V.path_metric(d, sym)}")
+    assert differing == 0
+    assert V.path_metric(d, sym) == best
+    assert V.path_metric(st.bits, sym) <= best                               # (what was sent is a path too)
+
+
+@pytest.mark.parametrize("h,esn0", ML_CASES)
+def test_model_is_maximum_likelihood(h, esn0):
+    """The model's sub-block decoding of the two frames where they were sent is the full-stream ML decoding bit for bit, its path
+    metric is M* (whatever the tie rules), and channel_errors is the header's count on those bits."""
+    import viterbi_ref as V
+    from meteor_demod_amd import frames
+    st, soft, sym, d, best = V.ml_case(False, h, esn0)
+    cadu, fr = frames.model_viterbi(soft, [frames.Frame(p, h, 0, 0, 0, 0) for p in st.positions])
+    bits = V.bits_of(cadu)
+    differing, metric = int((bits != d).sum()), V.path_metric(bits, sym)
+    want_errors = [V.channel_errors(d[p: p + FRAME], sym[p: p + FRAME]) for p in st.positions]
+    print(f"h {h}, {esn0} dB: {_ml_errors(st, d, esn0)} of {len(d)} bits of the ML decoding differ from what was sent; model != ML in {differing}; "
+          f"M* {best}, the model's path {metric}; channel_errors {[f.channel_errors for f in fr]}")
+    assert metric == best
+    assert differing == 0
+    assert [f.channel_errors for f in fr] == want_errors
+
+
+@pytest.mark.parametrize("h", [0, 3, 6])
+def test_model_is_maximum_likelihood_off_the_streams_ends(h):
+    """777 bits lead and 300 trail: no window is aligned to an end of the stream.  The frames' bits are the matching slices of the
+    full-stream ML decoding."""
+    import viterbi_ref as V
+    from meteor_demod_amd import frames
+    st, soft, sym, d, best = V.ml_case(False, h, 2.0, 777, 300)
+    assert st.positions == [777, 777 + FRAME] and len(sym) == 777 + 2 * FRAME + 300
+    cadu, fr = frames.model_viterbi(soft, [frames.Frame(p, h, 0, 0, 0, 0) for p in st.positions])
+    for c, f, p in zip(cadu, fr, st.positions):
+        differing, errors = int((V.bits_of(c) != d[p: p + FRAME]).sum()), int((d[p: p + FRAME] != st.bits[p: p + FRAME]).sum())
+        print(f"h {h}, frame at {p}: {errors} of {FRAME} bits of the ML decoding differ from what was sent; model != ML in {differing}; M* {best}; "
+              f"channel_errors {f.channel_errors}")
+        assert errors >= 10
+        assert differing == 0
+        assert f.channel_errors == V.channel_errors(d[p: p + FRAME], sym[p: p + FRAME])
+
+
+def test_model_on_ties_and_full_scale_equals_the_windowed_rule():
+    """Inputs where the tie rules decide: all zeros (every bit 0: on equal metrics the branch from s' >> 1 wins, and the lowest of
+    the equal final states), symbols of -1 / 0 / 1, the full int8 range with -128.  The model's bytes and channel_errors are those of
+    the header's rule in numpy (viterbi_ref.windowed_decode): on noise the windows need not merge, so the reference is the windowed
+    one.  A full-scale signal through the negating hypotheses comes back as sent with 0 channel errors."""
+    import viterbi_ref as V
+    from meteor_demod_amd import frames
+    for name, soft, at in V.hostile_inputs():
+        at = [at[k] for k in (0, 3, 5, 6)]
+        cadu, fr = frames.model_viterbi(soft, [frames.Frame(p, h, 0, 0, 0, 0) for p, h in at])
+        for c, f, (p, h) in zip(cadu, fr, at):
+            sym = V.through_H(soft, h)
+            want = V.windowed_decode(sym, p)[0]
+            differing = int((V.bits_of(c) != want).sum())
+            print(f"{name}: frame at {p} through h {h}: {int(want.sum())} ones, model != windowed rule in {differing}, channel_errors {f.channel_errors}")
+            assert differing == 0
+            assert f.channel_errors == V.channel_errors(want, sym[p: p + FRAME])
+            assert name != "zeros" or (not c.any() and f.channel_errors == 0)
+    st = U.Stream(seed=5, n_frames=1, lead=100, tail=100)
+    for h in (2, 3, 7):
+        soft = V.full_scale(st, h)
+        assert len(soft) == V.HOSTILE_M and (soft == -128).any()
+        cadu, fr = frames.model_viterbi(soft, [frames.Frame(100, h, 0, 0, 0, 0)])
+        assert bytes(cadu[0]) == st.frames[0] and fr[0].channel_errors == 0
 
 
 # --------------------------------------------------------------------------------------------------------------- tracker

@@ -1,7 +1,8 @@
 """CPU tests of the frame layer's link variant (include/meteor_demod_amd_frames_link.h: differential coding, a one-symbol skew
 between the rails): the differential pattern against a numpy derivation, the host model (csrc/frames_host.cpp,
-csrc/frames_link_host.cpp) against transmitted data it must recover through every combined hypothesis, polarity, the edges of a
-stream, ties, the tracker over (r, H), refusals, keywords, exports and layout, the C host's --diff / --skew against a stub, the
+csrc/frames_link_host.cpp) against transmitted data it must recover through every combined hypothesis, its decoder against an
+independent full-stream maximum-likelihood reference (tests/viterbi_ref.py), polarity, the edges of a stream, ties, the tracker
+over (r, H), refusals, keywords, exports and layout, the C host's --diff / --skew against a stub, the
 plain layer's blindness to these streams, and a sanitizer fuzz of the model and the tracker.  No GPU is touched."""
 from __future__ import annotations
 
@@ -115,6 +116,88 @@ def test_the_plain_layer_finds_none_of_it(streams):
         print(f"differential {differential}, H {H}: the plain layer finds {len(fr)} frames, {right} of them as sent")
         assert right == 0
         assert [bytes(c) for c in frames.model_decode(soft, differential=differential, skew=True)[0]] == st.frames
+
+
+# ------------------------------------------------------------------------------------------- the decoder is maximum-likelihood
+# viterbi_ref.ml_stream through the link sender: two frames that tile a stream of 16 384 symbols, sent through the inverse of H with
+# receive seed 400 + H at 2 dB and 500 + H at 3 dB.  s = 0, 1, 2 with h swapped and not, both modes; under `differential` H = 2 and 15
+# are sent upside down and decoded as their partners 0 and 13.  Measured for these seeds (bits of the full-stream ML decoding, NRZ-M
+# undone, that differ from what was sent, of 16 384): plain coding H 3: 25, 9: 89, 12: 102, 18: 52, 21: 140; differential H 0: 133,
+# 5: 78, 9: 134, 12: 63, 16: 102, 21: 105, 2: 83, 15: 43 at 2 dB; 12 (H 9) and 12 (differential, H 16) at 3 dB; windowed rule against
+# full-stream decoding: 0 differing bits in all fifteen (no seed had to be replaced).
+LINK_ML_CASES = ([(False, H, 2.0) for H in (3, 9, 12, 18, 21)] + [(True, H, 2.0) for H in (0, 5, 9, 12, 16, 21, 2, 15)]
+                 + [(False, 9, 3.0), (True, 16, 3.0)])
+
+
+def _ml_errors(st, bits, esn0):
+    """The premise of a 2 dB case: the ML decoder itself errs, at least 10 times over the stream."""
+    errors = int((bits != st.bits).sum())
+    assert esn0 != 2.0 or errors >= 10, errors
+    return errors
+
+
+@pytest.mark.parametrize("differential,H,esn0", LINK_ML_CASES)
+def test_reference_windowed_rule_equals_full_stream_decoding(differential, H, esn0):
+    """viterbi_ref itself, on the link streams: the header's sub-block rule in numpy - with `differential` the xor with the bit before
+    taken inside each sub-block's own decoding - gives the bits of one decoding of the whole stream."""
+    import viterbi_ref as V
+    st, _, sym, d, best = V.ml_case(differential, H, esn0)
+    want = V.nrzm_undo(d) if differential else d
+    parts = [V.windowed_decode(sym, p, differential) for p in st.positions]
+    differing = int((np.concatenate([b for b, _ in parts]) != want).sum()), int((np.concatenate([own for _, own in parts]) != d).sum())
+    print(f"H {H} (differential {differential}), {esn0} dB: {_ml_errors(st, want, esn0)} of {len(d)} bits of the ML decoding differ from what was sent; "
+          f"windowed != full-stream in {differing[0]} (the decoder's own bits: {differing[1]}); M* {best}")
+    assert differing == (0, 0)
+    assert V.path_metric(d, sym) == best
+
+
+@pytest.mark.parametrize("differential,H,esn0", LINK_ML_CASES)
+def test_model_is_maximum_likelihood(differential, H, esn0):
+    """The model's CADU bits of the two frames where they were sent are the full-stream ML decoding (NRZ-M undone under
+    `differential`) bit for bit; the decoder's own bits d - the model's output coded again from the 0 that stands before step 0 -
+    reach M*; and channel_errors is the header's count on d."""
+    import viterbi_ref as V
+    from meteor_demod_amd import frames
+    st, soft, sym, d, best = V.ml_case(differential, H, esn0)
+    want = V.nrzm_undo(d) if differential else d
+    Hc = L.canonical(H, differential)
+    cadu, fr = frames.model_viterbi(soft, [frames.Frame(p, Hc, 0, 0, 0, 0) for p in st.positions], differential=differential, skew=True)
+    bits = V.bits_of(cadu)
+    own = L.nrzm(bits) if differential else bits
+    differing, metric = int((bits != want).sum()), V.path_metric(own, sym)
+    print(f"H {H} as {Hc} (differential {differential}), {esn0} dB: {_ml_errors(st, want, esn0)} of {len(d)} bits of the ML decoding differ from what was "
+          f"sent; model != ML in {differing}; M* {best}, the model's path {metric}; channel_errors {[f.channel_errors for f in fr]}")
+    assert metric == best
+    assert differing == 0
+    assert [f.channel_errors for f in fr] == [V.channel_errors(d[p: p + FRAME], sym[p: p + FRAME]) for p in st.positions]
+
+
+def test_model_on_ties_and_full_scale_equals_the_windowed_rule():
+    """All zeros, symbols of -1 / 0 / 1 and the full int8 range with -128 through combined hypotheses of every skew, with and
+    without `differential`: the model's bytes and channel_errors are those of the header's rule in numpy.  Frames at 0 (no bit
+    before step 0) and at m - 8192 (the late rail is read at index m) are among them."""
+    import viterbi_ref as V
+    from meteor_demod_amd import frames
+    for differential, hyps in ((True, (9, 16, 5, 20)), (False, (18, 11, 7, 12))):
+        for name, soft, at in V.hostile_inputs():
+            at = [(at[i][0], H) for i, H in zip((0, 7, 3, 5), hyps)]
+            assert [p for p, _ in at][:2] == [0, len(soft) - FRAME]
+            cadu, fr = frames.model_viterbi(soft, [frames.Frame(p, H, 0, 0, 0, 0) for p, H in at], differential=differential, skew=True)
+            for c, f, (p, H) in zip(cadu, fr, at):
+                sym = V.through_H(soft, H)
+                want, own = V.windowed_decode(sym, p, differential)
+                differing = int((V.bits_of(c) != want).sum())
+                print(f"{name} (differential {differential}): frame at {p} through H {H}: {int(want.sum())} ones, model != windowed rule in {differing}, "
+                      f"channel_errors {f.channel_errors}")
+                assert differing == 0
+                assert f.channel_errors == V.channel_errors(own, sym[p: p + FRAME])
+                assert name != "zeros" or (not c.any() and f.channel_errors == 0)
+    st = L.LinkStream(seed=5, n_frames=1, lead=100, tail=100, differential=True)
+    for H in (1 + 8, 4 + 16, 2 + 8):                                           # h = 1 and 4 negate a rail: -128 is read as +128; 10 is sent upside down and read through 8
+        soft = V.full_scale(st, H)
+        assert len(soft) == V.HOSTILE_M and (soft == -128).any()
+        cadu, fr = frames.model_viterbi(soft, [frames.Frame(100, L.canonical(H, True), 0, 0, 0, 0)], differential=True, skew=True)
+        assert bytes(cadu[0]) == st.frames[0] and fr[0].channel_errors == 0
 
 
 # -------------------------------------------------------------------------------------------------------------- polarity

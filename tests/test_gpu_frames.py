@@ -1,8 +1,9 @@
 """GPU tests of the frame layer (include/meteor_demod_amd_frames.h): the two kernels against the host model, byte for byte - the
 marker search on random symbols, framed streams through the eight hypotheses at 7 dB (against the transmitted bytes too) and at
-3 dB (where the decoder errs, and the tie rules show), the edges of a stream, guard regions, the pieces of the host entry, a
-recording through the GPU demodulator and the GPU frame layer, and the C host's --cadu.  Every test prints the figures it asserts
-on."""
+3 dB (where the decoder errs, and the tie rules show), the decoder alone against an independent maximum-likelihood reference
+(tests/viterbi_ref.py) at 2 dB and against the model on ties, full-scale symbols and frame lists no tracker makes, the edges of a
+stream, guard regions, the pieces of the host entry, a recording through the GPU demodulator and the GPU frame layer, and the C
+host's --cadu.  Every test prints the figures it asserts on."""
 from __future__ import annotations
 
 import ctypes as C
@@ -160,6 +161,101 @@ def test_guard_regions(shift, stream, gpu_device):
     mc, mf = frames.model_viterbi(soft, sent)
     assert np.array_equal(o[pad:-64].reshape(-1, 1024), mc) and frames._frames(arr, len(sent)) == mf
     assert [bytes(x) for x in mc] == stream.frames
+
+
+# ------------------------------------------------------------------------------------------------ the decoder on its own
+@pytest.mark.parametrize("h", range(8))
+def test_viterbi_is_maximum_likelihood(h, gpu_device):
+    """Two frames that tile a stream of 16 384 symbols at 2 dB (test_frames_host.py's streams), decoded by the kernel where they were
+    sent: the bits of viterbi_ref's full-stream ML decoding, a path metric of M*, and the model's channel_errors (which are the
+    header's count on the reference's bits)."""
+    import viterbi_ref as V
+    from meteor_demod_amd import frames
+    st, soft, sym, d, best = V.ml_case(False, h, 2.0)
+    sent = [frames.Frame(p, h, 0, 0, 0, 0) for p in st.positions]
+    cadu, fr = frames.viterbi(_dev(soft.copy(), gpu_device), sent)
+    bits = V.bits_of(cadu.cpu().numpy())
+    errors, differing, metric = int((d != st.bits).sum()), int((bits != d).sum()), V.path_metric(bits, sym)
+    print(f"h {h}: {errors} of {len(d)} bits of the ML decoding differ from what was sent; kernel != ML in {differing}; M* {best}, the kernel's path "
+          f"{metric}; channel_errors {[f.channel_errors for f in fr]}")
+    assert errors >= 10
+    assert metric == best
+    assert differing == 0
+    assert fr == frames.model_viterbi(soft, sent)[1]
+    assert [f.channel_errors for f in fr] == [V.channel_errors(d[p: p + FRAME], sym[p: p + FRAME]) for p in st.positions]
+
+
+@pytest.mark.parametrize("kind", ["zeros", "ties", "full", "signal"])
+def test_viterbi_on_ties_and_full_scale(kind, gpu_device):
+    """8392 symbols the tracker would never call frames: all zeros (every metric ties at every step: every bit is 0), symbols of
+    -1 / 0 / 1, the full int8 range with -128; eight frames through the eight hypotheses in one launch.  And a clean frame at
+    +127 / -128 through the negating hypotheses 2, 3 and 7 (-128 is negated in int32): the sent bytes and 0 channel errors.  Bytes
+    and channel_errors are the model's (which test_frames_host.py holds to the header's rule on these inputs)."""
+    import viterbi_ref as V
+    from meteor_demod_amd import frames
+    if kind == "signal":
+        st = U.Stream(seed=5, n_frames=1, lead=100, tail=100)
+        cases = [(V.full_scale(st, h), [(100, h)]) for h in (2, 3, 7)]
+    else:
+        cases = [(s, a) for name, s, a in V.hostile_inputs() if name == kind]
+    for soft, at in cases:
+        assert len(soft) == V.HOSTILE_M
+        sent = [frames.Frame(p, h, 0, 0, 0, 0) for p, h in at]
+        cadu, fr = frames.viterbi(_dev(soft, gpu_device), sent)
+        mc, mf = frames.model_viterbi(soft, sent)
+        got = cadu.cpu().numpy()
+        print(f"{kind}: {int((soft == -128).sum())} values of -128; frames (position, h) {at}: ones per frame {[int(V.bits_of(c).sum()) for c in got]}, "
+              f"channel_errors {[f.channel_errors for f in fr]}")
+        assert np.array_equal(got, mc) and fr == mf
+        if kind == "zeros":
+            assert not got.any() and all(f.channel_errors == 0 for f in fr)
+        if kind == "signal":
+            assert (soft == -128).any() and bytes(got[0]) == st.frames[0] and fr[0].channel_errors == 0
+
+
+def _viterbi_between_canaries(d, m, sent, odd, gpu_device):
+    """mdemod_frames_viterbi_device on the stream in tensor `d` into a buffer of 0xA5 - the CADUs at an aligned address, or at an odd
+    one - whose first and last bytes must stay as they were: (uint8 [n, 1024], the frames with channel_errors)."""
+    import torch
+    from meteor_demod_amd import frames
+    arr = frames._to_c(sent)
+    pad = 64 + 3 * odd
+    out = torch.full((pad + len(sent) * 1024 + 64,), 0xA5, dtype=torch.uint8, device=d.device)
+    st = C.c_void_p(torch.cuda.current_stream(gpu_device).cuda_stream)
+    rc = frames.lib().mdemod_frames_viterbi_device(C.c_void_p(d.data_ptr()), m, arr, len(sent), C.c_void_p(out.data_ptr() + pad), gpu_device, st)
+    assert rc == 0
+    o = out.cpu().numpy()
+    assert (o[:pad] == 0xA5).all() and (o[-64:] == 0xA5).all()
+    return o[pad:-64].reshape(-1, 1024), frames._frames(arr, len(sent))
+
+
+def test_viterbi_takes_any_frame_list(gpu_device):
+    """Frame lists no tracker would make, on 2 x 8192 + 300 symbols: positions 0, 1, 127, 128, 129 (the lead-in clamped away, in part,
+    and whole), 8191, m - 8192, a position twice, two frames that share one symbol, hypotheses cycling 0..7; the whole list, the list
+    backwards, its first 1, 2 and 3 frames, and every frame alone; the CADUs at an aligned and at an odd address between canaries.
+    Bytes and channel_errors are the model's, the canaries stay, and a frame's result does not depend on what else is in the list."""
+    from meteor_demod_amd import frames
+    st = U.Stream(seed=9, n_frames=2, lead=150, tail=150)
+    soft = st.received(0, 3.0, seed=90)
+    m = len(soft)
+    assert m == 2 * FRAME + 300
+    at = [0, 1, 127, 128, 129, FRAME - 1, m - FRAME, 128, 150, 150 + FRAME - 1, 0]
+    sent = [frames.Frame(p, k % 8, 0, 0, 0, 0) for k, p in enumerate(at)]
+    mc, mf = frames.model_viterbi(soft, sent)
+    d = _dev(soft, gpu_device)
+    for odd in (0, 1):
+        cadu, fr = _viterbi_between_canaries(d, m, sent, odd, gpu_device)
+        assert np.array_equal(cadu, mc) and fr == mf, odd
+    cadu, fr = _viterbi_between_canaries(d, m, sent[::-1], 0, gpu_device)
+    assert np.array_equal(cadu, mc[::-1]) and fr == mf[::-1]
+    for n in (1, 2, 3):
+        cadu, fr = _viterbi_between_canaries(d, m, sent[:n], n & 1, gpu_device)
+        assert np.array_equal(cadu, mc[:n]) and fr == mf[:n], n
+    for k, f in enumerate(sent):
+        cadu, fr = _viterbi_between_canaries(d, m, [f], k & 1, gpu_device)
+        assert np.array_equal(cadu[0], mc[k]) and fr == [mf[k]], k
+    print(f"m {m}: {len(sent)} frames at {at}, channel_errors {[f.channel_errors for f in mf]}; the frame at 150, which is where and as one was sent, comes "
+          f"back as sent: {bytes(mc[8]) == st.frames[0]}")
 
 
 # ---------------------------------------------------------------------------------------------------------------- pieces

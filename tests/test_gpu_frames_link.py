@@ -1,6 +1,7 @@
 """GPU tests of the frame layer's link variant (include/meteor_demod_amd_frames_link.h): the link instances of the kernels against
 the host model, byte for byte - the marker search over all H on random symbols and at the edges of a stream, framed streams through
-every combined hypothesis at 3 dB, guard regions (the reads at index m), the pieces of the host entry (one symbol longer under
+every combined hypothesis at 3 dB, the decoder alone against an independent maximum-likelihood reference (tests/viterbi_ref.py) at
+2 dB and against the model on ties, full-scale symbols, frame lists no tracker makes and the two ends of a stream, guard regions (the reads at index m), the pieces of the host entry (one symbol longer under
 skew), the link entries with both switches off against the plain ones, an NRZ-M OQPSK recording through the GPU demodulator and the
 GPU frame layer at four carrier phases, and the C host's --skew --diff.  Every test prints the figures it asserts on."""
 from __future__ import annotations
@@ -144,6 +145,144 @@ def test_guard_regions(shift, gpu_device):
         print(f"shift {shift}, H {H}: channel_errors {[f.channel_errors for f in mf]}")
         assert np.array_equal(o[pad:-64].reshape(-1, 1024), mc) and frames._frames(arr, len(sent)) == mf
         assert [bytes(x) for x in mc] == st.frames
+
+
+# ------------------------------------------------------------------------------------------------ the decoder on its own
+def _hyps(sw):
+    """The combined hypotheses a mode allows."""
+    return [H for H in range(24 if sw["skew"] else 8) if not (sw["differential"] and H & 2)]
+
+
+@pytest.mark.parametrize("differential,H", [(False, 9), (False, 18), (False, 21), (True, 5), (True, 9), (True, 16), (True, 15)])
+def test_viterbi_is_maximum_likelihood(differential, H, gpu_device):
+    """Two frames that tile a stream of 16 384 symbols at 2 dB (test_frames_link_host.py's streams; both skews, h swapped and not,
+    H = 15 sent upside down and decoded as 13), decoded by the link kernel where they were sent: the bits of viterbi_ref's full-stream
+    ML decoding (NRZ-M undone under `differential`), the decoder's own bits - the output coded again from the 0 before step 0 -
+    with a path metric of M*, and the model's channel_errors (the header's count on the reference's d)."""
+    import viterbi_ref as V
+    from meteor_demod_amd import frames
+    sw = dict(differential=differential, skew=True)
+    st, soft, sym, d, best = V.ml_case(differential, H, 2.0)
+    want = V.nrzm_undo(d) if differential else d
+    sent = [frames.Frame(p, L.canonical(H, differential), 0, 0, 0, 0) for p in st.positions]
+    cadu, fr = frames.viterbi(_dev(soft.copy(), gpu_device), sent, **sw)
+    bits = V.bits_of(cadu.cpu().numpy())
+    own = L.nrzm(bits) if differential else bits
+    errors, differing, metric = int((want != st.bits).sum()), int((bits != want).sum()), V.path_metric(own, sym)
+    print(f"H {H} ({_name(sw)}): {errors} of {len(d)} bits of the ML decoding differ from what was sent; kernel != ML in {differing}; M* {best}, the "
+          f"kernel's path {metric}; channel_errors {[f.channel_errors for f in fr]}")
+    assert errors >= 10
+    assert metric == best
+    assert differing == 0
+    assert fr == frames.model_viterbi(soft, sent, **sw)[1]
+    assert [f.channel_errors for f in fr] == [V.channel_errors(d[p: p + FRAME], sym[p: p + FRAME]) for p in st.positions]
+
+
+@pytest.mark.parametrize("sw", SWITCHES, ids=_name)
+@pytest.mark.parametrize("kind", ["zeros", "ties", "full", "signal"])
+def test_viterbi_on_ties_and_full_scale(kind, sw, gpu_device):
+    """8392 symbols the tracker would never call frames: all zeros (every bit is 0), symbols of -1 / 0 / 1, the full int8 range with
+    -128; eight frames through eight of the mode's hypotheses in one launch, frames at 0 and at m - 8192 among them.  And a clean
+    frame at +127 / -128 through hypotheses that negate a rail (-128 is negated in int32): the sent bytes and 0 channel errors.
+    Bytes and channel_errors are the model's (which test_frames_link_host.py holds to the header's rule on these inputs)."""
+    import viterbi_ref as V
+    from meteor_demod_amd import frames
+    hyps = _hyps(sw)
+    if kind == "signal":
+        st = L.LinkStream(seed=5, n_frames=1, lead=100, tail=100, differential=sw["differential"])
+        cases = [(V.full_scale(st, H), [(100, H)]) for H in [H for H in hyps if H & 7 in (1, 4)][-3:]]
+    else:
+        cases = [(s, a) for name, s, a in V.hostile_inputs(tuple(hyps[::-3])) if name == kind]
+    for soft, at in cases:
+        assert len(soft) == V.HOSTILE_M
+        sent = [frames.Frame(p, H, 0, 0, 0, 0) for p, H in at]
+        cadu, fr = frames.viterbi(_dev(soft, gpu_device), sent, **sw)
+        mc, mf = frames.model_viterbi(soft, sent, **sw)
+        got = cadu.cpu().numpy()
+        print(f"{kind} ({_name(sw)}): {int((soft == -128).sum())} values of -128; frames (position, H) {at}: ones per frame "
+              f"{[int(V.bits_of(c).sum()) for c in got]}, channel_errors {[f.channel_errors for f in fr]}")
+        assert np.array_equal(got, mc) and fr == mf
+        if kind == "zeros":
+            assert not got.any() and all(f.channel_errors == 0 for f in fr)
+        if kind == "signal":
+            assert (soft == -128).any() and bytes(got[0]) == st.frames[0] and fr[0].channel_errors == 0
+
+
+def _viterbi_between_canaries(link, src, device, m, sent, odd, gpu_device):
+    """mdemod_frames_link_viterbi_device on the m symbols at address `src` into a buffer of 0xA5 - the CADUs at an aligned address, or
+    at an odd one - whose first and last bytes must stay as they were: (uint8 [n, 1024], the frames with channel_errors)."""
+    import torch
+    from meteor_demod_amd import frames
+    arr = frames._to_c(sent)
+    pad = 64 + 3 * odd
+    out = torch.full((pad + len(sent) * 1024 + 64,), 0xA5, dtype=torch.uint8, device=device)
+    st = C.c_void_p(torch.cuda.current_stream(gpu_device).cuda_stream)
+    rc = frames.lib().mdemod_frames_link_viterbi_device(C.byref(link), C.c_void_p(src), m, arr, len(sent), C.c_void_p(out.data_ptr() + pad), gpu_device, st)
+    assert rc == 0
+    o = out.cpu().numpy()
+    assert (o[:pad] == 0xA5).all() and (o[-64:] == 0xA5).all()
+    return o[pad:-64].reshape(-1, 1024), frames._frames(arr, len(sent))
+
+
+@pytest.mark.parametrize("sw", SWITCHES, ids=_name)
+def test_viterbi_takes_any_frame_list(sw, gpu_device):
+    """Frame lists no tracker would make, on 2 x 8192 + 300 symbols: positions 0, 1, 127, 128, 129, 8191, m - 8192, a position twice,
+    two frames that share one symbol, the mode's hypotheses in turn; the whole list, the list backwards, its first 1, 2 and 3 frames,
+    and every frame alone; the CADUs at an aligned and at an odd address between canaries.  Bytes and channel_errors are the model's,
+    the canaries stay, and a frame's result does not depend on what else is in the list."""
+    from meteor_demod_amd import frames
+    st = L.LinkStream(seed=9, n_frames=2, lead=150, tail=150, differential=sw["differential"])
+    hyps = _hyps(sw)
+    soft = st.received(hyps[-1], 3.0, seed=90)
+    m = len(soft)
+    assert m == 2 * FRAME + 300
+    at = [0, 1, 127, 128, 129, FRAME - 1, m - FRAME, 128, 150, 150 + FRAME - 1, 0]
+    sent = [frames.Frame(p, hyps[(k + 3) % len(hyps)] if k != 8 else hyps[-1], 0, 0, 0, 0) for k, p in enumerate(at)]
+    mc, mf = frames.model_viterbi(soft, sent, **sw)
+    d, link = _dev(soft, gpu_device), frames.make_link(**sw)
+    run = lambda frames_, odd: _viterbi_between_canaries(link, d.data_ptr(), d.device, m, frames_, odd, gpu_device)   # noqa: E731
+    for odd in (0, 1):
+        cadu, fr = run(sent, odd)
+        assert np.array_equal(cadu, mc) and fr == mf, odd
+    cadu, fr = run(sent[::-1], 0)
+    assert np.array_equal(cadu, mc[::-1]) and fr == mf[::-1]
+    for n in (1, 2, 3):
+        cadu, fr = run(sent[:n], n & 1)
+        assert np.array_equal(cadu, mc[:n]) and fr == mf[:n], n
+    for k, f in enumerate(sent):
+        cadu, fr = run([f], k & 1)
+        assert np.array_equal(cadu[0], mc[k]) and fr == [mf[k]], k
+    print(f"{_name(sw)}, m {m}: {len(sent)} frames (position, H) {[(f.position, f.hypothesis) for f in sent]}, channel_errors {[f.channel_errors for f in mf]}; "
+          f"the frame at 150, which is where and as one was sent, comes back as sent: {bytes(mc[8]) == st.frames[0]}")
+
+
+@pytest.mark.parametrize("differential", [False, True])
+@pytest.mark.parametrize("H", [8, 9, 16, 17])
+def test_viterbi_at_the_ends_of_the_stream(H, differential, gpu_device):
+    """Two frames and nothing else at 3 dB, the stream at an odd address between canaries of +-127.  The frame at m - 8192 under s = 1
+    and s = 2 with h even and odd reads its late rail at index m, which is 0 and not the canary: the symbol that follows the stream
+    reads +127 on both rails through h, so that channel_errors would count it (a hard decision of 0 is "not positive").  The frame
+    at 0 has no lead-in, and with `differential` no bit before step 0.  Bytes and channel_errors are the model's, for both frames
+    in one launch and for each alone."""
+    from meteor_demod_amd import frames
+    sw = dict(differential=differential, skew=True)
+    st = L.LinkStream(seed=7, n_frames=2, lead=0, tail=0, differential=differential)
+    soft = st.received(H, 3.0, seed=70 + H)
+    m = len(soft)
+    buf = np.where(np.random.default_rng(H).integers(0, 2, 4096 + 2 * m + 4096) > 0, 127, -127).astype(np.int8)
+    start = 2048 + 1001
+    buf[start: start + 2 * m] = soft.reshape(-1)
+    buf[start + 2 * m: start + 2 * m + 2] = U.through_inverse(np.array([[127, 127]]), H & 7)[0]
+    d, link = _dev(buf, gpu_device), frames.make_link(**sw)
+    sent = [frames.Frame(0, H, 0, 0, 0, 0), frames.Frame(m - FRAME, H, 0, 0, 0, 0)]
+    mc, mf = frames.model_viterbi(soft, sent, **sw)
+    cadu, fr = _viterbi_between_canaries(link, d.data_ptr() + start, d.device, m, sent, 1, gpu_device)
+    wrong = [int((np.unpackbits(c) != np.unpackbits(np.frombuffer(f, dtype=np.uint8))).sum()) for c, f in zip(cadu, st.frames)]
+    print(f"H {H} ({_name(sw)}): channel_errors {[f.channel_errors for f in fr]}, bits that differ from what was sent {wrong}")
+    assert np.array_equal(cadu, mc) and fr == mf
+    for k in (0, 1):
+        alone, fa = _viterbi_between_canaries(link, d.data_ptr() + start, d.device, m, [sent[k]], 0, gpu_device)
+        assert np.array_equal(alone[0], mc[k]) and fa == [mf[k]]
 
 
 # ---------------------------------------------------------------------------------------------------------------- pieces
