@@ -43,6 +43,10 @@
  * word found, followed and stripped and the 36 branches undone on the GPU (branch delay --int-delay, 2048 by default), one more
  * line on stdout.  Independent of --diff; --skew is accepted and ignored beside it, because the sync word resolves the skew.  Only
  * with --cadu / --vcdu.  Weak references.
+ * --image goes on from the VCDUs (include/meteor_demod_amd_image.h): the packet zone demultiplexed and the MSU-MR image packets
+ * decoded on the GPU, one <output without .s>_<apid>.pgm (binary P5, 1568 wide) per active channel that received a strip, one more
+ * line on stdout.  It implies the --vcdu pass; the .vcdu and the .cadu are written only when asked for.  --apids a,b,c chooses the
+ * active channels.  Weak references; refused with --stdout.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -65,6 +69,7 @@
 #include "meteor_demod_amd_frames_link.h"
 #include "meteor_demod_amd_rs.h"
 #include "meteor_demod_amd_interleave.h"
+#include "meteor_demod_amd_image.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
 #endif
@@ -98,7 +103,7 @@ static const struct option longopts[] = {
 	{ "tui-selftest", 0, NULL, 0x08 }, { "tui", 0, NULL, 0x09 }, { "jobs", 1, NULL, 0x0a },
 	{ "offset", 1, NULL, 0x0b },    { "decimate", 1, NULL, 0x0c }, { "scan", 0, NULL, 0x0d },
 	{ "cadu", 0, NULL, 0x0e },      { "vcdu", 0, NULL, 0x0f },    { "diff", 0, NULL, 0x10 },    { "skew", 0, NULL, 0x11 },
-	{ "int", 0, NULL, 0x12 },       { "int-delay", 1, NULL, 0x13 },
+	{ "int", 0, NULL, 0x12 },       { "int-delay", 1, NULL, 0x13 }, { "image", 0, NULL, 0x14 },   { "apids", 1, NULL, 0x15 },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -169,6 +174,24 @@ have_rs(void)
 {
 	return mdemod_rs_default_opts && mdemod_rs_decode_host && mdemod_rs_vcdu_header;
 }
+
+/* the image layer's entries (include/meteor_demod_amd_image.h: --image): weak as well */
+#pragma weak mdemod_image_default_opts
+#pragma weak mdemod_image_decode_host
+#pragma weak mdemod_image_free
+
+static int
+have_image(void)
+{
+	return mdemod_image_default_opts && mdemod_image_decode_host && mdemod_image_free;
+}
+
+/* what --vcdu / --image ask of the transfer frames of one file */
+struct vcdu_req {
+	int      write_vcdu;                 /* the .vcdu and its line */
+	int      image;                      /* the pictures and their line */
+	uint32_t apids[3];
+};
 
 /* --offset: a signed number of Hz with an optional k / M suffix (fractions kept); 1 on a malformed one */
 static int
@@ -246,6 +269,13 @@ usage(const char *prog)
 	        "                           frame i of the .vcdu is frame i of the .cadu); one more line on stdout: frames,\n"
 	        "                           uncorrectable frames, bytes corrected, frames and counter gaps per VCID.  The .cadu\n"
 	        "                           is written only with --cadu.  Not with --stdout\n"
+	        "       --image             Pictures as well: the packet zone of the transfer frames demultiplexed into CCSDS packets\n"
+	        "                           and the MSU-MR image packets decoded on the GPU; every active channel that received a\n"
+	        "                           strip is written as <output>_<apid>.pgm (binary P5, 1568 wide, 8 bit); one more line on\n"
+	        "                           stdout: packets, image packets per APID, strips truncated, lines, share of cells\n"
+	        "                           filled.  Implies the --vcdu pass; the .vcdu / .cadu are written only with --vcdu /\n"
+	        "                           --cadu.  Not with --stdout\n"
+	        "       --apids <a,b,c>     With --image: the three active channels, each 64 .. 69 (default: 64,65,66)\n"
 	        "       --diff              With --cadu / --vcdu: the sender codes differentially (NRZ-M); the frame pass searches\n"
 	        "                           the differential marker and undoes the coding after the Viterbi decoder\n"
 	        "       --skew              With --cadu / --vcdu: the rails may stand one symbol apart, as after -m oqpsk when\n"
@@ -755,9 +785,49 @@ beside(const char *s_name, const char *ext)
 	return out;
 }
 
-/* --vcdu: n CADUs through the transfer-frame layer, the VCDUs beside the output file, one line.  0, or the exit status. */
+/* --image: n VCDUs through the image layer, one PGM per active channel that received a strip beside the output file, one line.
+ * 0, or the exit status. */
 static int
-vcdu_file(const char *s_name, const uint8_t *cadu, uint64_t n, int device)
+image_files(const char *s_name, const uint8_t *vcdu, const mdemod_rs_info *info, uint64_t n, int device, const uint32_t apids[3])
+{
+	mdemod_image_opts io;
+	mdemod_image_result res;
+	mdemod_image_default_opts(&io);
+	for (int k = 0; k < 3; k++) io.apids[k] = apids[k];
+	const int rc = mdemod_image_decode_host(&io, vcdu, info, n, &res, device);
+	if (rc != MDEMOD_OK) { fprintf(stderr, "--image: %s: %s\n", s_name, why_of(rc)); return 2; }
+	int code = 0;
+	const uint32_t rows = res.summary.rows;
+	for (int k = 0; k < 3 && !code; k++) {
+		int any = 0;
+		for (uint64_t c = 0; c < (uint64_t)rows * MDEMOD_IMAGE_CELLS && !any; c++) any = res.filled[k][c];
+		if (!any) continue;
+		char ext[32];
+		snprintf(ext, sizeof ext, "_%u.pgm", (unsigned)apids[k]);
+		char *name = beside(s_name, ext);
+		FILE *o = name ? fopen(name, "wb") : NULL;
+		if (!o) { fprintf(stderr, "--image: could not open %s\n", name ? name : "the picture"); free(name); code = 1; break; }
+		const size_t bytes = (size_t)rows * 8 * MDEMOD_IMAGE_WIDTH;
+		const int short_write = fprintf(o, "P5\n%d %u\n255\n", MDEMOD_IMAGE_WIDTH, rows * 8) < 0 || fwrite(res.image[k], 1, bytes, o) != bytes;
+		if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--image: writing %s failed: the picture is incomplete\n", name); code = 1; }
+		free(name);
+	}
+	if (!code) {
+		char *base = beside(s_name, "");
+		printf("%s: %llu packets; image packets", base ? base : s_name, (unsigned long long)res.summary.packets);
+		for (int k = 0; k < 3; k++) printf("%s apid %u: %llu", k ? "," : "", (unsigned)apids[k], (unsigned long long)res.summary.per_apid[apids[k] - 64]);
+		printf("; %llu strips truncated; %u lines; %.1f %% of cells filled\n", (unsigned long long)res.summary.truncated, rows * 8,
+		       rows ? 100.0 * (double)res.summary.cells_filled / (3.0 * rows * MDEMOD_IMAGE_CELLS) : 0.0);
+		free(base);
+	}
+	mdemod_image_free(&res);
+	return code;
+}
+
+/* --vcdu / --image: n CADUs through the transfer-frame layer; the VCDUs beside the output file and one line (--vcdu), the pictures
+ * (--image).  0, or the exit status. */
+static int
+vcdu_file(const char *s_name, const uint8_t *cadu, uint64_t n, int device, const struct vcdu_req *req)
 {
 	uint8_t *vcdu = malloc(n ? (size_t)n * MDEMOD_RS_VCDU_BYTES : 1);
 	mdemod_rs_info *info = calloc(n ? (size_t)n : 1, sizeof(*info));
@@ -768,6 +838,7 @@ vcdu_file(const char *s_name, const uint8_t *cadu, uint64_t n, int device)
 	mdemod_rs_default_opts(&ro);
 	const int rc = mdemod_rs_decode_host(&ro, cadu, n, vcdu, info, device);
 	if (rc != MDEMOD_OK) { fprintf(stderr, "--vcdu: %s: %s\n", s_name, why_of(rc)); code = 2; goto done; }
+	if (!req->write_vcdu) { code = image_files(s_name, vcdu, info, n, device, req->apids); goto done; }
 	FILE *o = fopen(out_name, "wb");
 	if (!o) { fprintf(stderr, "--vcdu: could not open %s\n", out_name); goto done; }
 	const int short_write = fwrite(vcdu, MDEMOD_RS_VCDU_BYTES, (size_t)n, o) != (size_t)n;
@@ -793,7 +864,7 @@ vcdu_file(const char *s_name, const uint8_t *cadu, uint64_t n, int device)
 	for (int v = 0; v < 64; v++)
 		if (seen[v]) { printf("%s vcid %d: %llu frames, %llu counter gaps", any ? "," : "", v, (unsigned long long)per[v], (unsigned long long)gaps[v]); any = 1; }
 	printf("%s\n", any ? "" : " no VCID");
-	code = 0;
+	code = req->image ? image_files(s_name, vcdu, info, n, device, req->apids) : 0;
 done:
 	free(out_name); free(info); free(vcdu);
 	return code;
@@ -802,7 +873,7 @@ done:
 /* --cadu / --vcdu: the soft symbols of one finished output file through the frame layer, the CADUs (and the VCDUs) beside it.  0, or
  * the exit status. */
 static int
-cadu_file(const char *s_name, int device, int write_cadu, int write_vcdu, int diff, int skew, uint32_t il_delay)
+cadu_file(const char *s_name, int device, int write_cadu, const struct vcdu_req *req, int diff, int skew, uint32_t il_delay)
 {
 	FILE *f = fopen(s_name, "rb");
 	if (!f) { fprintf(stderr, "--cadu: %s: %s\n", s_name, strerror(errno)); return 1; }
@@ -846,7 +917,7 @@ cadu_file(const char *s_name, int device, int write_cadu, int write_vcdu, int di
 	                            : mdemod_frames_decode_host(&fo, sym, m, cadu, frames, cap, &n, device);
 	if (rc != MDEMOD_OK) { fprintf(stderr, "--cadu: %s: %s\n", s_name, why_of(rc)); code = 2; goto done; }
 	if (n > cap) n = cap;
-	if (!write_cadu) { code = vcdu_file(s_name, cadu, n, device); goto done; }
+	if (!write_cadu) { code = vcdu_file(s_name, cadu, n, device, req); goto done; }
 	FILE *o = fopen(out_name, "wb");
 	if (!o) { fprintf(stderr, "--cadu: could not open %s\n", out_name); goto done; }
 	const int short_write = fwrite(cadu, MDEMOD_FRAME_BYTES, (size_t)n, o) != (size_t)n;
@@ -860,7 +931,7 @@ cadu_file(const char *s_name, int device, int write_cadu, int write_vcdu, int di
 	}
 	printf("%s: %llu frames (%llu flywheel) in %u runs, mean channel errors %.1f / %d\n", out_name, (unsigned long long)n, (unsigned long long)fly, runs,
 	       n ? (double)errors / (double)n : 0.0, MDEMOD_FRAME_DECISIONS);
-	code = write_vcdu ? vcdu_file(s_name, cadu, n, device) : 0;
+	code = req->write_vcdu || req->image ? vcdu_file(s_name, cadu, n, device, req) : 0;
 done:
 	free(out_name); free(frames); free(cadu); free(soft); free(segs); free(deint);
 	fclose(f);
@@ -878,7 +949,8 @@ main(int argc, char **argv)
 	int devs[MAX_DEVICES], n_dev = 0, plan = 0, jobs = 4;
 	int use_fe = 0, decimation = 1;
 	double offset_hz = 0.0;
-	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0, want_vcdu = 0, want_diff = 0, want_skew = 0, want_int = 0;
+	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0, want_vcdu = 0, want_diff = 0, want_skew = 0, want_int = 0, want_image = 0, apids_given = 0;
+	struct vcdu_req vreq = { 0, 0, { 64, 65, 66 } };
 	long int_delay = MDEMOD_IL_DEFAULT_BRANCH_DELAY;
 	double *auto_offsets = NULL;               /* --offset auto: the offset chosen for each file */
 #ifdef MDEMOD_TUI
@@ -908,6 +980,21 @@ main(int argc, char **argv)
 		case 0x11: want_skew = 1; break;
 		case 0x12: want_int = 1; break;
 		case 0x13: int_delay = atol(optarg); break;
+		case 0x14: want_image = 1; break;
+		case 0x15: {
+			unsigned a[3];
+			char tail;
+			if (sscanf(optarg, "%u,%u,%u%c", &a[0], &a[1], &a[2], &tail) != 3) { fprintf(stderr, "--apids: three numbers, e.g. 64,65,66\n"); return 1; }
+			for (int k = 0; k < 3; k++) {
+				if (a[k] < 64 || a[k] > 69 || (k && a[k] == a[0]) || (k == 2 && a[2] == a[1])) {
+					fprintf(stderr, "--apids: three different channels, each 64 .. 69\n");
+					return 1;
+				}
+				vreq.apids[k] = a[k];
+			}
+			apids_given = 1;
+			break;
+		}
 		case 0x0b:
 			if (!strcmp(optarg, "auto")) { auto_offset = 1; use_fe = 1; break; }
 			auto_offset = 0;
@@ -991,7 +1078,23 @@ main(int argc, char **argv)
 		        have_frames() ? "meteor_demod_amd_rs.h" : "meteor_demod_amd_frames.h");
 		return 1;
 	}
-	if ((want_diff || want_skew) && !(want_cadu || want_vcdu)) {
+	if (apids_given && !want_image) {
+		fprintf(stderr, "--apids: only with --image (it chooses the channels of the pictures)\n");
+		return 1;
+	}
+	if (want_image && stdout_mode) {
+		fprintf(stderr, "--image: not with --stdout (the frames are decoded from the finished output file)\n");
+		return 1;
+	}
+	if (want_image && !(have_frames() && have_rs() && have_image())) {
+		fprintf(stderr, "--image: this library has no %s (built without include/%s's entries)\n",
+		        !have_frames() ? "frame layer" : !have_rs() ? "transfer-frame layer" : "image layer",
+		        !have_frames() ? "meteor_demod_amd_frames.h" : !have_rs() ? "meteor_demod_amd_rs.h" : "meteor_demod_amd_image.h");
+		return 1;
+	}
+	vreq.write_vcdu = want_vcdu;
+	vreq.image = want_image;
+	if ((want_diff || want_skew) && !(want_cadu || want_vcdu || want_image)) {
 		fprintf(stderr, "--diff / --skew: only with --cadu or --vcdu (they change how the frames are found and decoded, not the soft symbols)\n");
 		return 1;
 	}
@@ -999,7 +1102,7 @@ main(int argc, char **argv)
 		fprintf(stderr, "--int: not with --stdout (the frames are decoded from the finished output file)\n");
 		return 1;
 	}
-	if (want_int && !(want_cadu || want_vcdu)) {
+	if (want_int && !(want_cadu || want_vcdu || want_image)) {
 		fprintf(stderr, "--int: only with --cadu or --vcdu (it changes how the frames are found and decoded, not the soft symbols)\n");
 		return 1;
 	}
@@ -1216,7 +1319,7 @@ main(int argc, char **argv)
 	for (int d = 0; d < n_dev; d++) if (ws[d].rc > rc_all) rc_all = ws[d].rc;
 	/* (the workers closed their files through their own copies of the stream_io entries: nothing of the originals is open any more) */
 	for (int i = 0; i < n_files; i++) { io[i].in = NULL; io[i].out = NULL; }
-	if ((want_cadu || want_vcdu) && rc_all == 0)
-		for (int i = 0; i < n_files && rc_all == 0; i++) rc_all = cadu_file(io[i].out_name, devs[i % n_dev], want_cadu, want_vcdu, want_diff, want_skew, want_int ? (uint32_t)int_delay : 0);
+	if ((want_cadu || want_vcdu || want_image) && rc_all == 0)
+		for (int i = 0; i < n_files && rc_all == 0; i++) rc_all = cadu_file(io[i].out_name, devs[i % n_dev], want_cadu, &vreq, want_diff, want_skew, want_int ? (uint32_t)int_delay : 0);
 	LEAVE(rc_all);
 }
