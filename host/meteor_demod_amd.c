@@ -47,6 +47,10 @@
  * decoded on the GPU, one <output without .s>_<apid>.pgm (binary P5, 1568 wide) per active channel that received a strip, one more
  * line on stdout.  It implies the --vcdu pass; the .vcdu and the .cadu are written only when asked for.  --apids a,b,c chooses the
  * active channels.  Weak references; refused with --stdout.
+ * --rectify and --composite go on from the pictures (include/meteor_demod_amd_picture.h): every channel's picture resampled to equal
+ * ground distance and contrast-stretched as <output without .s>_<apid>_rect.pgm, and three channels as one colour picture
+ * <output without .s>_<abc>.ppm (binary P6) with one more line on stdout.  --altitude and --scan-angle set the geometry of
+ * --rectify.  Only with --image.  Weak references.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -70,6 +74,7 @@
 #include "meteor_demod_amd_rs.h"
 #include "meteor_demod_amd_interleave.h"
 #include "meteor_demod_amd_image.h"
+#include "meteor_demod_amd_picture.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
 #endif
@@ -104,6 +109,7 @@ static const struct option longopts[] = {
 	{ "offset", 1, NULL, 0x0b },    { "decimate", 1, NULL, 0x0c }, { "scan", 0, NULL, 0x0d },
 	{ "cadu", 0, NULL, 0x0e },      { "vcdu", 0, NULL, 0x0f },    { "diff", 0, NULL, 0x10 },    { "skew", 0, NULL, 0x11 },
 	{ "int", 0, NULL, 0x12 },       { "int-delay", 1, NULL, 0x13 }, { "image", 0, NULL, 0x14 },   { "apids", 1, NULL, 0x15 },
+	{ "rectify", 0, NULL, 0x16 },   { "composite", 1, NULL, 0x17 }, { "altitude", 1, NULL, 0x18 }, { "scan-angle", 1, NULL, 0x19 },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -186,11 +192,27 @@ have_image(void)
 	return mdemod_image_default_opts && mdemod_image_decode_host && mdemod_image_free;
 }
 
+/* the picture layer's entries (include/meteor_demod_amd_picture.h: --rectify, --composite): weak as well */
+#pragma weak mdemod_picture_default_opts
+#pragma weak mdemod_picture_column_map
+#pragma weak mdemod_picture_compose_host
+#pragma weak mdemod_picture_free
+
+static int
+have_picture(void)
+{
+	return mdemod_picture_default_opts && mdemod_picture_compose_host && mdemod_picture_free;
+}
+
 /* what --vcdu / --image ask of the transfer frames of one file */
 struct vcdu_req {
 	int      write_vcdu;                 /* the .vcdu and its line */
 	int      image;                      /* the pictures and their line */
 	uint32_t apids[3];
+	int      rectify;                    /* --rectify: one _rect.pgm per channel; the composite is rectified too */
+	int      composite;                  /* 0: none, 1: the slots of comp[], 2: auto */
+	uint32_t comp[3];                    /* slots (0 .. 2) of R, G, B */
+	double   altitude_km, scan_deg;      /* 0: the library's default */
 };
 
 /* --offset: a signed number of Hz with an optional k / M suffix (fractions kept); 1 on a malformed one */
@@ -276,6 +298,16 @@ usage(const char *prog)
 	        "                           filled.  Implies the --vcdu pass; the .vcdu / .cadu are written only with --vcdu /\n"
 	        "                           --cadu.  Not with --stdout\n"
 	        "       --apids <a,b,c>     With --image: the three active channels, each 64 .. 69 (default: 64,65,66)\n"
+	        "       --rectify           With --image: every channel that received a strip also as <output>_<apid>_rect.pgm,\n"
+	        "                           resampled on the GPU to equal ground distance (the Earth's curvature taken out; wider\n"
+	        "                           than 1568) and contrast-stretched between the 0.5 % and 99.5 % points of its pixels\n"
+	        "       --composite <abc>   With --image: a colour picture <output>_<abc>.ppm (binary P6); a, b, c are the channels\n"
+	        "                           of red, green and blue, each 1 .. 3, counted in --apids order (e.g. 321); stretched,\n"
+	        "                           and rectified when --rectify is given; one more line on stdout: width, lines, the\n"
+	        "                           stretch limits per plane, the share of valid pixels.  --composite auto: 321 when all\n"
+	        "                           three channels received a strip, 221 when only the first two did, otherwise none\n"
+	        "       --altitude <km>     With --rectify: the orbit's altitude (300 .. 2000, default: 820)\n"
+	        "       --scan-angle <deg>  With --rectify: the scanner's full scan angle (1 .. 130, default: 110)\n"
 	        "       --diff              With --cadu / --vcdu: the sender codes differentially (NRZ-M); the frame pass searches\n"
 	        "                           the differential marker and undoes the coding after the Viterbi decoder\n"
 	        "       --skew              With --cadu / --vcdu: the rails may stand one symbol apart, as after -m oqpsk when\n"
@@ -785,11 +817,81 @@ beside(const char *s_name, const char *ext)
 	return out;
 }
 
+/* --rectify / --composite: the pictures of one file through the picture layer.  One <apid>_rect.pgm per channel that received a
+ * strip (--rectify), one <abc>.ppm and its line (--composite).  0, or the exit status. */
+static int
+picture_files(const char *s_name, const mdemod_image_result *res, const struct vcdu_req *req, int device)
+{
+	const uint32_t rows = res->summary.rows;
+	const uint8_t *image[3] = { res->image[0], res->image[1], res->image[2] }, *filled[3] = { res->filled[0], res->filled[1], res->filled[2] };
+	int got[3] = { 0, 0, 0 }, code = 0;
+	for (int k = 0; k < 3; k++)
+		for (uint64_t c = 0; c < (uint64_t)rows * MDEMOD_IMAGE_CELLS && !got[k]; c++) got[k] = res->filled[k][c];
+	mdemod_picture_opts po;
+	mdemod_picture_default_opts(&po);
+	po.rectify = req->rectify ? 1 : 0;
+	if (req->altitude_km != 0.0) po.altitude_km = req->altitude_km;
+	if (req->scan_deg != 0.0) po.scan_deg = req->scan_deg;
+	for (int k = 0; k < 3 && !code && req->rectify; k++) {
+		if (!got[k]) continue;
+		const uint32_t select[1] = { (uint32_t)k };
+		mdemod_picture_result pic;
+		const int rc = mdemod_picture_compose_host(&po, image, filled, rows, select, 1, &pic, device);
+		if (rc != MDEMOD_OK) { fprintf(stderr, "--rectify: %s: %s\n", s_name, why_of(rc)); return rc == MDEMOD_ERR_PARAM ? 1 : 2; }
+		char ext[32];
+		snprintf(ext, sizeof ext, "_%u_rect.pgm", (unsigned)req->apids[k]);
+		char *name = beside(s_name, ext);
+		FILE *o = name ? fopen(name, "wb") : NULL;
+		if (!o) { fprintf(stderr, "--rectify: could not open %s\n", name ? name : "the picture"); code = 1; }
+		else {
+			const size_t bytes = (size_t)pic.lines * pic.width;
+			const int short_write = fprintf(o, "P5\n%u %u\n255\n", pic.width, pic.lines) < 0 || fwrite(pic.pixels, 1, bytes, o) != bytes;
+			if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--rectify: writing %s failed: the picture is incomplete\n", name); code = 1; }
+		}
+		free(name);
+		mdemod_picture_free(&pic);
+	}
+	if (code || !req->composite) return code;
+	uint32_t select[3] = { req->comp[0], req->comp[1], req->comp[2] };
+	char *base = beside(s_name, "");
+	if (req->composite == 2) {
+		if (got[0] && got[1] && got[2]) { select[0] = 2; select[1] = 1; select[2] = 0; }
+		else if (got[0] && got[1]) { select[0] = 1; select[1] = 1; select[2] = 0; }
+		else {
+			printf("%s: no composite (--composite auto wants strips in all three channels, or in the first two)\n", base ? base : s_name);
+			free(base);
+			return 0;
+		}
+	}
+	mdemod_picture_result pic;
+	const int rc = mdemod_picture_compose_host(&po, image, filled, rows, select, 3, &pic, device);
+	if (rc != MDEMOD_OK) { fprintf(stderr, "--composite: %s: %s\n", s_name, why_of(rc)); free(base); return rc == MDEMOD_ERR_PARAM ? 1 : 2; }
+	char ext[32];
+	snprintf(ext, sizeof ext, "_%u%u%u.ppm", (unsigned)select[0] + 1, (unsigned)select[1] + 1, (unsigned)select[2] + 1);
+	char *name = beside(s_name, ext);
+	FILE *o = name ? fopen(name, "wb") : NULL;
+	if (!o) { fprintf(stderr, "--composite: could not open %s\n", name ? name : "the picture"); code = 1; }
+	else {
+		const size_t bytes = (size_t)pic.lines * pic.width * 3;
+		const int short_write = fprintf(o, "P6\n%u %u\n255\n", pic.width, pic.lines) < 0 || (bytes && fwrite(pic.pixels, 1, bytes, o) != bytes);
+		if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--composite: writing %s failed: the picture is incomplete\n", name); code = 1; }
+	}
+	if (!code)
+		printf("%s: composite %u%u%u: %u x %u%s; stretch R %u .. %u, G %u .. %u, B %u .. %u; %.1f %% of pixels valid\n", base ? base : s_name,
+		       (unsigned)select[0] + 1, (unsigned)select[1] + 1, (unsigned)select[2] + 1, pic.width, pic.lines, req->rectify ? " rectified" : "",
+		       pic.lo[0], pic.hi[0], pic.lo[1], pic.hi[1], pic.lo[2], pic.hi[2],
+		       rows ? 100.0 * (double)pic.valid_cells / ((double)rows * pic.width) : 0.0);
+	free(name); free(base);
+	mdemod_picture_free(&pic);
+	return code;
+}
+
 /* --image: n VCDUs through the image layer, one PGM per active channel that received a strip beside the output file, one line.
  * 0, or the exit status. */
 static int
-image_files(const char *s_name, const uint8_t *vcdu, const mdemod_rs_info *info, uint64_t n, int device, const uint32_t apids[3])
+image_files(const char *s_name, const uint8_t *vcdu, const mdemod_rs_info *info, uint64_t n, int device, const struct vcdu_req *req)
 {
+	const uint32_t *apids = req->apids;
 	mdemod_image_opts io;
 	mdemod_image_result res;
 	mdemod_image_default_opts(&io);
@@ -820,6 +922,7 @@ image_files(const char *s_name, const uint8_t *vcdu, const mdemod_rs_info *info,
 		       rows ? 100.0 * (double)res.summary.cells_filled / (3.0 * rows * MDEMOD_IMAGE_CELLS) : 0.0);
 		free(base);
 	}
+	if (!code && (req->rectify || req->composite)) code = picture_files(s_name, &res, req, device);
 	mdemod_image_free(&res);
 	return code;
 }
@@ -838,7 +941,7 @@ vcdu_file(const char *s_name, const uint8_t *cadu, uint64_t n, int device, const
 	mdemod_rs_default_opts(&ro);
 	const int rc = mdemod_rs_decode_host(&ro, cadu, n, vcdu, info, device);
 	if (rc != MDEMOD_OK) { fprintf(stderr, "--vcdu: %s: %s\n", s_name, why_of(rc)); code = 2; goto done; }
-	if (!req->write_vcdu) { code = image_files(s_name, vcdu, info, n, device, req->apids); goto done; }
+	if (!req->write_vcdu) { code = image_files(s_name, vcdu, info, n, device, req); goto done; }
 	FILE *o = fopen(out_name, "wb");
 	if (!o) { fprintf(stderr, "--vcdu: could not open %s\n", out_name); goto done; }
 	const int short_write = fwrite(vcdu, MDEMOD_RS_VCDU_BYTES, (size_t)n, o) != (size_t)n;
@@ -864,7 +967,7 @@ vcdu_file(const char *s_name, const uint8_t *cadu, uint64_t n, int device, const
 	for (int v = 0; v < 64; v++)
 		if (seen[v]) { printf("%s vcid %d: %llu frames, %llu counter gaps", any ? "," : "", v, (unsigned long long)per[v], (unsigned long long)gaps[v]); any = 1; }
 	printf("%s\n", any ? "" : " no VCID");
-	code = req->image ? image_files(s_name, vcdu, info, n, device, req->apids) : 0;
+	code = req->image ? image_files(s_name, vcdu, info, n, device, req) : 0;
 done:
 	free(out_name); free(info); free(vcdu);
 	return code;
@@ -949,8 +1052,8 @@ main(int argc, char **argv)
 	int devs[MAX_DEVICES], n_dev = 0, plan = 0, jobs = 4;
 	int use_fe = 0, decimation = 1;
 	double offset_hz = 0.0;
-	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0, want_vcdu = 0, want_diff = 0, want_skew = 0, want_int = 0, want_image = 0, apids_given = 0;
-	struct vcdu_req vreq = { 0, 0, { 64, 65, 66 } };
+	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0, want_vcdu = 0, want_diff = 0, want_skew = 0, want_int = 0, want_image = 0, apids_given = 0, geometry_given = 0;
+	struct vcdu_req vreq = { 0, 0, { 64, 65, 66 }, 0, 0, { 2, 1, 0 }, 0.0, 0.0 };
 	long int_delay = MDEMOD_IL_DEFAULT_BRANCH_DELAY;
 	double *auto_offsets = NULL;               /* --offset auto: the offset chosen for each file */
 #ifdef MDEMOD_TUI
@@ -993,6 +1096,25 @@ main(int argc, char **argv)
 				vreq.apids[k] = a[k];
 			}
 			apids_given = 1;
+			break;
+		}
+		case 0x16: vreq.rectify = 1; break;
+		case 0x17:
+			if (!strcmp(optarg, "auto")) { vreq.composite = 2; break; }
+			if (strlen(optarg) != 3 || strspn(optarg, "123") != 3) {
+				fprintf(stderr, "--composite: three digits, each 1 .. 3 (the channels of red, green, blue in --apids order, e.g. 321), or auto\n");
+				return 1;
+			}
+			for (int k = 0; k < 3; k++) vreq.comp[k] = (uint32_t)(optarg[k] - '1');
+			vreq.composite = 1;
+			break;
+		case 0x18:
+		case 0x19: {
+			char *end;
+			const double v = strtod(optarg, &end);
+			if (end == optarg || *end || !(v > 0.0)) { fprintf(stderr, "%s: a positive number\n", c == 0x18 ? "--altitude" : "--scan-angle"); return 1; }
+			if (c == 0x18) vreq.altitude_km = v; else vreq.scan_deg = v;
+			geometry_given = 1;
 			break;
 		}
 		case 0x0b:
@@ -1091,6 +1213,30 @@ main(int argc, char **argv)
 		        !have_frames() ? "frame layer" : !have_rs() ? "transfer-frame layer" : "image layer",
 		        !have_frames() ? "meteor_demod_amd_frames.h" : !have_rs() ? "meteor_demod_amd_rs.h" : "meteor_demod_amd_image.h");
 		return 1;
+	}
+	if ((vreq.rectify || vreq.composite) && !want_image) {
+		fprintf(stderr, "--rectify / --composite: only with --image (they work on its pictures)\n");
+		return 1;
+	}
+	if (geometry_given && !vreq.rectify) {
+		fprintf(stderr, "--altitude / --scan-angle: only with --rectify (they are the geometry it takes out)\n");
+		return 1;
+	}
+	if ((vreq.rectify || vreq.composite) && !have_picture()) {
+		fprintf(stderr, "--rectify / --composite: this library has no picture layer (built without include/meteor_demod_amd_picture.h's entries)\n");
+		return 1;
+	}
+	if (vreq.rectify) {
+		/* the geometry is refused before anything is demodulated */
+		mdemod_picture_opts po;
+		mdemod_picture_default_opts(&po);
+		if (vreq.altitude_km != 0.0) po.altitude_km = vreq.altitude_km;
+		if (vreq.scan_deg != 0.0) po.scan_deg = vreq.scan_deg;
+		uint32_t w = 0;
+		if (!mdemod_picture_column_map || mdemod_picture_column_map(&po, NULL, 0, &w) != MDEMOD_OK) {
+			fprintf(stderr, "--rectify: %s\n", mdemod_picture_column_map ? mdemod_last_error() : "this library has no column map");
+			return 1;
+		}
 	}
 	vreq.write_vcdu = want_vcdu;
 	vreq.image = want_image;
