@@ -51,6 +51,12 @@
  * ground distance and contrast-stretched as <output without .s>_<apid>_rect.pgm, and three channels as one colour picture
  * <output without .s>_<abc>.ppm (binary P6) with one more line on stdout.  --altitude and --scan-angle set the geometry of
  * --rectify.  Only with --image.  Weak references.
+ * --map puts the pictures on a latitude / longitude grid (include/meteor_demod_amd_map.h): the packets' onboard time stamps and a
+ * two-line element set geolocate every line, and the GPU resamples the channels north-up.  With --composite one
+ * <output without .s>_<abc>_map.ppm, without it one <output without .s>_<apid>_map.pgm per channel that received a strip; beside
+ * each a world file of the same name ending in .wld, and one more line on stdout.  --norad, --map-scale, --date, --time-offset and
+ * --scan-side set its options; --scan-angle applies, --altitude is not consulted (the orbit's radius comes from the element set).
+ * Only with --image.  Weak references.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -75,6 +81,7 @@
 #include "meteor_demod_amd_interleave.h"
 #include "meteor_demod_amd_image.h"
 #include "meteor_demod_amd_picture.h"
+#include "meteor_demod_amd_map.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
 #endif
@@ -110,6 +117,8 @@ static const struct option longopts[] = {
 	{ "cadu", 0, NULL, 0x0e },      { "vcdu", 0, NULL, 0x0f },    { "diff", 0, NULL, 0x10 },    { "skew", 0, NULL, 0x11 },
 	{ "int", 0, NULL, 0x12 },       { "int-delay", 1, NULL, 0x13 }, { "image", 0, NULL, 0x14 },   { "apids", 1, NULL, 0x15 },
 	{ "rectify", 0, NULL, 0x16 },   { "composite", 1, NULL, 0x17 }, { "altitude", 1, NULL, 0x18 }, { "scan-angle", 1, NULL, 0x19 },
+	{ "map", 1, NULL, 0x1a },       { "norad", 1, NULL, 0x1b },   { "map-scale", 1, NULL, 0x1c }, { "date", 1, NULL, 0x1d },
+	{ "time-offset", 1, NULL, 0x1e }, { "scan-side", 1, NULL, 0x1f },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -204,6 +213,19 @@ have_picture(void)
 	return mdemod_picture_default_opts && mdemod_picture_compose_host && mdemod_picture_free;
 }
 
+/* the map layer's entries (include/meteor_demod_amd_map.h: --map): weak as well */
+#pragma weak mdemod_map_default_opts
+#pragma weak mdemod_map_parse_tle
+#pragma weak mdemod_map_fit_time
+#pragma weak mdemod_map_compose_host
+#pragma weak mdemod_map_free
+
+static int
+have_map(void)
+{
+	return mdemod_map_default_opts && mdemod_map_parse_tle && mdemod_map_fit_time && mdemod_map_compose_host && mdemod_map_free;
+}
+
 /* what --vcdu / --image ask of the transfer frames of one file */
 struct vcdu_req {
 	int      write_vcdu;                 /* the .vcdu and its line */
@@ -213,6 +235,12 @@ struct vcdu_req {
 	int      composite;                  /* 0: none, 1: the slots of comp[], 2: auto */
 	uint32_t comp[3];                    /* slots (0 .. 2) of R, G, B */
 	double   altitude_km, scan_deg;      /* 0: the library's default */
+	int      map;                        /* --map: the pictures on a latitude / longitude grid */
+	mdemod_map_tle tle;                  /* the element set of --map (and --norad) */
+	double   map_scale, time_offset;     /* --map-scale (0: the default); --time-offset when offset_given */
+	int      offset_given, date_given;
+	int32_t  map_date;                   /* --date: days since 1970-01-01 */
+	int      side;                       /* --scan-side: 0 for the default */
 };
 
 /* --offset: a signed number of Hz with an optional k / M suffix (fractions kept); 1 on a malformed one */
@@ -308,6 +336,17 @@ usage(const char *prog)
 	        "                           three channels received a strip, 221 when only the first two did, otherwise none\n"
 	        "       --altitude <km>     With --rectify: the orbit's altitude (300 .. 2000, default: 820)\n"
 	        "       --scan-angle <deg>  With --rectify: the scanner's full scan angle (1 .. 130, default: 110)\n"
+	        "       --map <tle file>    With --image: the pictures on a north-up latitude / longitude grid (EPSG:4326), from the\n"
+	        "                           packets' onboard time stamps and the two-line element set of the file (a circular orbit\n"
+	        "                           with the secular J2 terms, not SGP4): with --composite <output>_<abc>_map.ppm, without\n"
+	        "                           it one <output>_<apid>_map.pgm per channel that received a strip; beside each a world\n"
+	        "                           file ending in .wld; one more line on stdout: size, scale, corners, the fitted row\n"
+	        "                           period, the UTC of the first line, the share of valid pixels.  --scan-angle applies\n"
+	        "       --norad <id>        With --map: the catalogue number of the set to take (default: the file's first)\n"
+	        "       --map-scale <n>     With --map: pixels per degree of latitude (1 .. 1000, default: 100)\n"
+	        "       --date <yyyy-mm-dd> With --map: the date of the first line's onboard time (default: the one nearest the epoch)\n"
+	        "       --time-offset <s>   With --map: onboard clock minus UTC in seconds (default: 10800, Moscow time)\n"
+	        "       --scan-side <1|-1>  With --map: which way the mirror turns (default: 1)\n"
 	        "       --diff              With --cadu / --vcdu: the sender codes differentially (NRZ-M); the frame pass searches\n"
 	        "                           the differential marker and undoes the coding after the Viterbi decoder\n"
 	        "       --skew              With --cadu / --vcdu: the rails may stand one symbol apart, as after -m oqpsk when\n"
@@ -886,6 +925,113 @@ picture_files(const char *s_name, const mdemod_image_result *res, const struct v
 	return code;
 }
 
+/* days since 1970-01-01 to a civil date */
+static void
+civil_from_days(int64_t z, int *y, unsigned *m, unsigned *d)
+{
+	z += 719468;
+	const int64_t era = (z >= 0 ? z : z - 146096) / 146097;
+	const unsigned doe = (unsigned)(z - era * 146097), yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;
+	const unsigned doy = doe - (365 * yoe + yoe / 4 - yoe / 100), mp = (5 * doy + 2) / 153;
+	*d = doy - (153 * mp + 2) / 5 + 1;
+	*m = mp < 10 ? mp + 3 : mp - 9;
+	*y = (int)((int64_t)yoe + era * 400 + (*m <= 2));
+}
+
+static int64_t
+days_from_civil(int64_t y, unsigned m, unsigned d)
+{
+	y -= m <= 2;
+	const int64_t era = (y >= 0 ? y : y - 399) / 400;
+	const unsigned yoe = (unsigned)(y - era * 400), doy = (153 * (m + (m > 2 ? -3 : 9)) + 2) / 5 + d - 1, doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
+	return era * 146097 + (int64_t)doe - 719468;
+}
+
+/* the options of --map as the layer takes them */
+static void
+map_options(const struct vcdu_req *req, mdemod_map_opts *mo)
+{
+	mdemod_map_default_opts(mo);
+	if (req->scan_deg != 0.0) mo->scan_deg = req->scan_deg;
+	if (req->map_scale != 0.0) mo->px_per_deg = req->map_scale;
+	if (req->offset_given) mo->time_offset = req->time_offset;
+	if (req->date_given) mo->date = req->map_date;
+	if (req->side) mo->side = req->side;
+}
+
+/* one map of the given slots: <tag>_map.ppm / .pgm, its world file and its line.  0, or the exit status. */
+static int
+map_file(const char *s_name, const mdemod_image_result *res, const struct vcdu_req *req, const uint32_t *select, uint32_t planes, const char *tag, int device)
+{
+	const uint8_t *image[3] = { res->image[0], res->image[1], res->image[2] }, *filled[3] = { res->filled[0], res->filled[1], res->filled[2] };
+	mdemod_map_opts mo;
+	mdemod_map_result map;
+	map_options(req, &mo);
+	const int rc = mdemod_map_compose_host(&mo, &req->tle, image, filled, res->summary.rows, res->place, res->sinfo, res->n_packets, select, planes, &map, device);
+	if (rc != MDEMOD_OK) { fprintf(stderr, "--map: %s: %s\n", s_name, why_of(rc)); return rc == MDEMOD_ERR_PARAM ? 1 : 2; }
+	int code = 0;
+	char ext[48];
+	snprintf(ext, sizeof ext, "_%s_map.%s", tag, planes == 3 ? "ppm" : "pgm");
+	char *name = beside(s_name, ext), *base = beside(s_name, "");
+	FILE *o = name ? fopen(name, "wb") : NULL;
+	if (!o) { fprintf(stderr, "--map: could not open %s\n", name ? name : "the picture"); code = 1; }
+	else {
+		const size_t bytes = (size_t)map.height * map.width * planes;
+		const int short_write = fprintf(o, "P%d\n%u %u\n255\n", planes == 3 ? 6 : 5, map.width, map.height) < 0 || fwrite(map.pixels, 1, bytes, o) != bytes;
+		if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--map: writing %s failed: the picture is incomplete\n", name); code = 1; }
+	}
+	free(name);
+	snprintf(ext, sizeof ext, "_%s_map.wld", tag);
+	name = code ? NULL : beside(s_name, ext);
+	o = name ? fopen(name, "w") : NULL;
+	if (!code && !o) { fprintf(stderr, "--map: could not open %s\n", name ? name : "the world file"); code = 1; }
+	else if (!code) {
+		const int short_write = fprintf(o, "%.17g\n0\n0\n%.17g\n%.17g\n%.17g\n", 1.0 / map.sx, -1.0 / map.sy, map.lon_left + 0.5 / map.sx, map.lat_top - 0.5 / map.sy) < 0;
+		if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--map: writing %s failed: the world file is incomplete\n", name); code = 1; }
+	}
+	free(name);
+	if (!code) {
+		const double total = (double)map.timing.date * 86400.0 + map.utc0, day = floor(total / 86400.0), sec = total - day * 86400.0;
+		int y; unsigned m, d;
+		civil_from_days((int64_t)day, &y, &m, &d);
+		printf("%s: map %s: %u x %u at %u x %g px/deg; lat %.4f .. %.4f, lon %.4f .. %.4f; row period %.6f s over %u rows; first line %04d-%02u-%02uT%02d:%02d:%06.3fZ; "
+		       "%.1f %% of pixels valid\n", base ? base : s_name, tag, map.width, map.height, map.sx, map.sy, map.lat_top - map.height / map.sy, map.lat_top,
+		       map.lon_left, map.lon_left + (double)map.width / map.sx, map.timing.row_period, map.timing.rows_fit, y, m, d, (int)(sec / 3600.0),
+		       (int)(fmod(sec, 3600.0) / 60.0), fmod(sec, 60.0), 100.0 * (double)map.valid_pixels / ((double)map.width * map.height));
+	}
+	free(base);
+	mdemod_map_free(&map);
+	return code;
+}
+
+/* --map: the composite (--composite) or every channel that received a strip on the grid.  0, or the exit status. */
+static int
+map_files(const char *s_name, const mdemod_image_result *res, const struct vcdu_req *req, int device)
+{
+	const uint32_t rows = res->summary.rows;
+	int got[3] = { 0, 0, 0 }, code = 0;
+	for (int k = 0; k < 3; k++)
+		for (uint64_t c = 0; c < (uint64_t)rows * MDEMOD_IMAGE_CELLS && !got[k]; c++) got[k] = res->filled[k][c];
+	char tag[16];
+	if (req->composite) {
+		uint32_t select[3] = { req->comp[0], req->comp[1], req->comp[2] };
+		if (req->composite == 2) {
+			if (got[0] && got[1] && got[2]) { select[0] = 2; select[1] = 1; select[2] = 0; }
+			else if (got[0] && got[1]) { select[0] = 1; select[1] = 1; select[2] = 0; }
+			else return 0;                                                         /* (the composite's own line has said so) */
+		}
+		snprintf(tag, sizeof tag, "%u%u%u", (unsigned)select[0] + 1, (unsigned)select[1] + 1, (unsigned)select[2] + 1);
+		return map_file(s_name, res, req, select, 3, tag, device);
+	}
+	for (int k = 0; k < 3 && !code; k++) {
+		if (!got[k]) continue;
+		const uint32_t select[1] = { (uint32_t)k };
+		snprintf(tag, sizeof tag, "%u", (unsigned)req->apids[k]);
+		code = map_file(s_name, res, req, select, 1, tag, device);
+	}
+	return code;
+}
+
 /* --image: n VCDUs through the image layer, one PGM per active channel that received a strip beside the output file, one line.
  * 0, or the exit status. */
 static int
@@ -923,6 +1069,7 @@ image_files(const char *s_name, const uint8_t *vcdu, const mdemod_rs_info *info,
 		free(base);
 	}
 	if (!code && (req->rectify || req->composite)) code = picture_files(s_name, &res, req, device);
+	if (!code && req->map) code = map_files(s_name, &res, req, device);
 	mdemod_image_free(&res);
 	return code;
 }
@@ -1052,7 +1199,9 @@ main(int argc, char **argv)
 	int devs[MAX_DEVICES], n_dev = 0, plan = 0, jobs = 4;
 	int use_fe = 0, decimation = 1;
 	double offset_hz = 0.0;
-	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0, want_vcdu = 0, want_diff = 0, want_skew = 0, want_int = 0, want_image = 0, apids_given = 0, geometry_given = 0;
+	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0, want_vcdu = 0, want_diff = 0, want_skew = 0, want_int = 0, want_image = 0, apids_given = 0, geometry_given = 0, altitude_given = 0, map_opts_given = 0;
+	const char *map_fname = NULL;
+	uint32_t map_norad = 0;
 	struct vcdu_req vreq = { 0, 0, { 64, 65, 66 }, 0, 0, { 2, 1, 0 }, 0.0, 0.0 };
 	long int_delay = MDEMOD_IL_DEFAULT_BRANCH_DELAY;
 	double *auto_offsets = NULL;               /* --offset auto: the offset chosen for each file */
@@ -1113,10 +1262,47 @@ main(int argc, char **argv)
 			char *end;
 			const double v = strtod(optarg, &end);
 			if (end == optarg || *end || !(v > 0.0)) { fprintf(stderr, "%s: a positive number\n", c == 0x18 ? "--altitude" : "--scan-angle"); return 1; }
-			if (c == 0x18) vreq.altitude_km = v; else vreq.scan_deg = v;
+			if (c == 0x18) { vreq.altitude_km = v; altitude_given = 1; } else vreq.scan_deg = v;
 			geometry_given = 1;
 			break;
 		}
+		case 0x1a: map_fname = optarg; break;
+		case 0x1b: {
+			char *end;
+			const long v = strtol(optarg, &end, 10);
+			if (end == optarg || *end || v < 1 || v > 999999999) { fprintf(stderr, "--norad: a catalogue number\n"); return 1; }
+			map_norad = (uint32_t)v;
+			map_opts_given = 1;
+			break;
+		}
+		case 0x1c:
+		case 0x1e: {
+			char *end;
+			const double v = strtod(optarg, &end);
+			if (end == optarg || *end) { fprintf(stderr, "%s: a number\n", c == 0x1c ? "--map-scale" : "--time-offset"); return 1; }
+			if (c == 0x1c) vreq.map_scale = v; else { vreq.time_offset = v; vreq.offset_given = 1; }
+			if (c == 0x1c && v == 0.0) vreq.map_scale = -1.0;                        /* (0 stands for the default inside: let the layer refuse it) */
+			map_opts_given = 1;
+			break;
+		}
+		case 0x1d: {
+			int y;
+			unsigned m, d;
+			char tail;
+			if (sscanf(optarg, "%d-%u-%u%c", &y, &m, &d, &tail) != 3 || y < 1957 || y > 2200 || m < 1 || m > 12 || d < 1 || d > 31) {
+				fprintf(stderr, "--date: yyyy-mm-dd\n");
+				return 1;
+			}
+			vreq.map_date = (int32_t)days_from_civil(y, m, d);
+			vreq.date_given = 1;
+			map_opts_given = 1;
+			break;
+		}
+		case 0x1f:
+			if (strcmp(optarg, "1") && strcmp(optarg, "-1")) { fprintf(stderr, "--scan-side: 1 or -1\n"); return 1; }
+			vreq.side = atoi(optarg);
+			map_opts_given = 1;
+			break;
 		case 0x0b:
 			if (!strcmp(optarg, "auto")) { auto_offset = 1; use_fe = 1; break; }
 			auto_offset = 0;
@@ -1200,6 +1386,10 @@ main(int argc, char **argv)
 		        have_frames() ? "meteor_demod_amd_rs.h" : "meteor_demod_amd_frames.h");
 		return 1;
 	}
+	if (map_fname && !(have_map() && have_picture())) {
+		fprintf(stderr, "--map: this library has no map layer (built without include/meteor_demod_amd_map.h's entries)\n");
+		return 1;
+	}
 	if (apids_given && !want_image) {
 		fprintf(stderr, "--apids: only with --image (it chooses the channels of the pictures)\n");
 		return 1;
@@ -1218,7 +1408,35 @@ main(int argc, char **argv)
 		fprintf(stderr, "--rectify / --composite: only with --image (they work on its pictures)\n");
 		return 1;
 	}
-	if (geometry_given && !vreq.rectify) {
+	if ((map_fname || map_opts_given) && !want_image) {
+		fprintf(stderr, "--map: only with --image (it works on its pictures and their time stamps)\n");
+		return 1;
+	}
+	if (map_opts_given && !map_fname) {
+		fprintf(stderr, "--norad / --map-scale / --date / --time-offset / --scan-side: only with --map (they are its options)\n");
+		return 1;
+	}
+	if (map_fname) {
+		/* the element set and the options are refused before anything is demodulated */
+		FILE *tf = fopen(map_fname, "rb");
+		static char text[65536];
+		const size_t got = tf ? fread(text, 1, sizeof text - 1, tf) : 0;
+		if (!tf || ferror(tf)) { fprintf(stderr, "--map: could not read %s\n", map_fname); if (tf) fclose(tf); return 1; }
+		fclose(tf);
+		text[got] = 0;
+		for (size_t k = 0; k < got; k++) if (!text[k]) text[k] = ' ';
+		if (mdemod_map_parse_tle(text, map_norad, &vreq.tle) != MDEMOD_OK) { fprintf(stderr, "--map: %s: %s\n", map_fname, mdemod_last_error()); return 1; }
+		mdemod_map_opts mo;
+		mdemod_map_timing none;
+		map_options(&vreq, &mo);
+		/* (a fit of no packets: options out of range are refused with their own text first) */
+		if (mdemod_map_fit_time(NULL, NULL, 0, &mo, &none) != MDEMOD_OK && strncmp(mdemod_last_error(), "map: no placed packet", 21)) {
+			fprintf(stderr, "--map: %s\n", mdemod_last_error());
+			return 1;
+		}
+		vreq.map = 1;
+	}
+	if (geometry_given && !vreq.rectify && (altitude_given || !map_fname)) {
 		fprintf(stderr, "--altitude / --scan-angle: only with --rectify (they are the geometry it takes out)\n");
 		return 1;
 	}

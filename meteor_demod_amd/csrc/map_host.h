@@ -1,0 +1,55 @@
+/*
+ * map_host.h — what csrc/map_host.cpp (host: TLE, orbit, time fit, geolocation, node grid, the model, the bands of the whole-map
+ * entry) and csrc/map.hip (the kernel and the device entries) share: the option check, the bands with a backend in the kernel's
+ * place, and the model's entries, exported for the tests.  Free of the GPU runtime.
+ */
+#ifndef MDEMOD_MAP_HOST_H
+#define MDEMOD_MAP_HOST_H
+
+#include "../../include/meteor_demod_amd_map.h"
+#include "picture_host.h"
+
+#define MAP_STEP       MDEMOD_MAP_NODE_STEP
+#define MAP_X_TOP      (PIC_LAST * 256)           /* the largest X inside the picture */
+
+/* opts (NULL: the defaults) checked and completed (piece_lines 0 -> 1024); MDEMOD_ERR_PARAM with a text otherwise */
+int  map_settings(const mdemod_map_opts *opts, mdemod_map_opts &out);
+
+/* rows, select, planes, width and height of a warp call; MDEMOD_ERR_PARAM with a text */
+int  map_check_warp(const char *who, uint32_t rows, const uint32_t *select, uint32_t planes, uint32_t width, uint32_t height);
+
+inline uint32_t map_node_count(uint32_t pixels) { return (pixels + MAP_STEP - 1) / MAP_STEP + 1; }
+
+/* what stands in the kernel's place in the whole-map entry.  begin: the selected slots (the others NULL), whole, and the nodes;
+ * histogram: of those slots; band: `height` lines from node row `node_row` on into host memory.  All synchronous. */
+struct MapBackend {
+	virtual int begin(const uint8_t *const image[3], const uint8_t *const filled[3], uint32_t rows, const mdemod_map_nodes &grid, uint32_t planes,
+	                  uint32_t piece_lines) = 0;
+	virtual int histogram(uint32_t *hist) = 0;
+	virtual int tables(const uint8_t *lut, uint32_t planes) = 0;
+	virtual int band(const uint32_t *select, uint32_t planes, uint32_t node_row, uint32_t height, uint8_t *out, uint8_t *valid) = 0;
+	virtual ~MapBackend() {}
+};
+
+int  map_compose_bands(const mdemod_map_opts &o, const mdemod_map_tle *tle, const uint8_t *const image[3], const uint8_t *const filled[3], uint32_t rows,
+                       const mdemod_placement *place, const mdemod_strip_info *sinfo, uint64_t n_desc, const uint32_t *select, uint32_t planes,
+                       mdemod_map_result *out, MapBackend &backend);
+
+/* the argument checks that mdemod_map_compose_host and the model's host entry share */
+int  map_check_compose(const char *who, const mdemod_map_tle *tle, const uint8_t *const image[3], const uint8_t *const filled[3], uint32_t rows,
+                       const mdemod_placement *place, const mdemod_strip_info *sinfo, uint64_t n_desc, const uint32_t *select, uint32_t planes,
+                       mdemod_map_result *out);
+
+extern "C" {
+
+/* the model of map_warp: host memory, the same rule */
+int  mdemod_map_model_warp(const uint8_t *const image[3], const uint8_t *const filled[3], uint32_t rows, const uint32_t *select, uint32_t planes,
+                           const uint8_t *lut, const int32_t *nodes, uint32_t width, uint32_t height, uint8_t *out, uint8_t *valid);
+/* mdemod_map_compose_host with the model in the kernel's place (no device) */
+int  mdemod_map_model_host(const mdemod_map_opts *opts, const mdemod_map_tle *tle, const uint8_t *const image[3], const uint8_t *const filled[3],
+                           uint32_t rows, const mdemod_placement *place, const mdemod_strip_info *sinfo, uint64_t n_desc, const uint32_t *select,
+                           uint32_t planes, mdemod_map_result *out);
+
+}
+
+#endif
