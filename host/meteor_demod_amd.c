@@ -57,6 +57,10 @@
  * each a world file of the same name ending in .wld, and one more line on stdout.  --norad, --map-scale, --date, --time-offset and
  * --scan-side set its options; --scan-angle applies, --altitude is not consulted (the orbit's radius comes from the element set).
  * Only with --image.  Weak references.
+ * --mosaic <base> goes on from there (include/meteor_demod_amd_mosaic.h): the pictures of all input files (1 .. 8 passes of one
+ * satellite) are kept after their own maps are written, and once every file is done they are blended onto one common grid on the
+ * first GPU: <base>_<tag>_mosaic.ppm / .pgm, its world file and one more line.  --mosaic-blend feather|best.  Only with --map.
+ * Weak references.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -82,6 +86,7 @@
 #include "meteor_demod_amd_image.h"
 #include "meteor_demod_amd_picture.h"
 #include "meteor_demod_amd_map.h"
+#include "meteor_demod_amd_mosaic.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
 #endif
@@ -118,7 +123,7 @@ static const struct option longopts[] = {
 	{ "int", 0, NULL, 0x12 },       { "int-delay", 1, NULL, 0x13 }, { "image", 0, NULL, 0x14 },   { "apids", 1, NULL, 0x15 },
 	{ "rectify", 0, NULL, 0x16 },   { "composite", 1, NULL, 0x17 }, { "altitude", 1, NULL, 0x18 }, { "scan-angle", 1, NULL, 0x19 },
 	{ "map", 1, NULL, 0x1a },       { "norad", 1, NULL, 0x1b },   { "map-scale", 1, NULL, 0x1c }, { "date", 1, NULL, 0x1d },
-	{ "time-offset", 1, NULL, 0x1e }, { "scan-side", 1, NULL, 0x1f },
+	{ "time-offset", 1, NULL, 0x1e }, { "scan-side", 1, NULL, 0x1f }, { "mosaic", 1, NULL, 0x20 },   { "mosaic-blend", 1, NULL, 0x21 },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -226,6 +231,17 @@ have_map(void)
 	return mdemod_map_default_opts && mdemod_map_parse_tle && mdemod_map_fit_time && mdemod_map_compose_host && mdemod_map_free;
 }
 
+/* the mosaic layer's entries (include/meteor_demod_amd_mosaic.h: --mosaic): weak as well */
+#pragma weak mdemod_mosaic_default_opts
+#pragma weak mdemod_mosaic_compose_host
+#pragma weak mdemod_mosaic_free
+
+static int
+have_mosaic(void)
+{
+	return mdemod_mosaic_default_opts && mdemod_mosaic_compose_host && mdemod_mosaic_free;
+}
+
 /* what --vcdu / --image ask of the transfer frames of one file */
 struct vcdu_req {
 	int      write_vcdu;                 /* the .vcdu and its line */
@@ -241,6 +257,10 @@ struct vcdu_req {
 	int      offset_given, date_given;
 	int32_t  map_date;                   /* --date: days since 1970-01-01 */
 	int      side;                       /* --scan-side: 0 for the default */
+	const char *tle_text;                /* the text of the file of --map, and the catalogue number of --norad (the mosaic takes these) */
+	uint32_t norad;
+	uint32_t mosaic_blend;               /* --mosaic-blend */
+	mdemod_image_result *keep;           /* --mosaic: where this file's pictures go instead of being freed (rows = 0: nothing kept) */
 };
 
 /* --offset: a signed number of Hz with an optional k / M suffix (fractions kept); 1 on a malformed one */
@@ -347,6 +367,15 @@ usage(const char *prog)
 	        "       --date <yyyy-mm-dd> With --map: the date of the first line's onboard time (default: the one nearest the epoch)\n"
 	        "       --time-offset <s>   With --map: onboard clock minus UTC in seconds (default: 10800, Moscow time)\n"
 	        "       --scan-side <1|-1>  With --map: which way the mirror turns (default: 1)\n"
+	        "       --mosaic <base>     With --map: the input files (1 .. 8) are passes of one satellite; besides each file's own\n"
+	        "                           maps all passes are blended onto one common grid on the first GPU, where several saw the\n"
+	        "                           same ground weighted by the distance from the edge of the swath: <base>_<abc>_mosaic.ppm\n"
+	        "                           with --composite (auto: on what the passes received together), without it one\n"
+	        "                           <base>_<apid>_mosaic.pgm per channel; beside each a world file ending in .wld; one more\n"
+	        "                           line on stdout: size, scale, corners, the passes with the UTC of their first lines, the\n"
+	        "                           share of valid pixels and of pixels seen by two or more passes.  The options of --map\n"
+	        "                           apply to every pass; a file without a picture is left out\n"
+	        "       --mosaic-blend <m>  With --mosaic: feather (default: the weighted mean) or best (the pass nearest its nadir)\n"
 	        "       --diff              With --cadu / --vcdu: the sender codes differentially (NRZ-M); the frame pass searches\n"
 	        "                           the differential marker and undoes the coding after the Viterbi decoder\n"
 	        "       --skew              With --cadu / --vcdu: the rails may stand one symbol apart, as after -m oqpsk when\n"
@@ -1032,6 +1061,110 @@ map_files(const char *s_name, const mdemod_image_result *res, const struct vcdu_
 	return code;
 }
 
+/* --mosaic: one mosaic of the given slots of the kept passes: <base>_<tag>_mosaic.ppm / .pgm, its world file and its line.  0, or
+ * the exit status. */
+static int
+mosaic_file(const char *base, const mdemod_mosaic_pass *passes, uint32_t n, const struct vcdu_req *req, const uint32_t *select, uint32_t planes, const char *tag,
+            int device)
+{
+	mdemod_mosaic_opts mo;
+	mdemod_mosaic_result mos;
+	mdemod_mosaic_default_opts(&mo);
+	if (req->scan_deg != 0.0) mo.scan_deg = req->scan_deg;
+	if (req->map_scale != 0.0) mo.px_per_deg = req->map_scale;
+	if (req->offset_given) mo.time_offset = req->time_offset;
+	if (req->side) mo.side = req->side;
+	mo.blend = req->mosaic_blend;
+	const int rc = mdemod_mosaic_compose_host(&mo, passes, n, select, planes, &mos, device);
+	if (rc != MDEMOD_OK) { fprintf(stderr, "--mosaic: %s\n", why_of(rc)); return rc == MDEMOD_ERR_PARAM ? 1 : 2; }
+	int code = 0;
+	const size_t len = strlen(base) + strlen(tag) + 32;
+	char *name = malloc(len);
+	if (name) snprintf(name, len, "%s_%s_mosaic.%s", base, tag, planes == 3 ? "ppm" : "pgm");
+	FILE *o = name ? fopen(name, "wb") : NULL;
+	if (!o) { fprintf(stderr, "--mosaic: could not open %s\n", name ? name : "the picture"); code = 1; }
+	else {
+		const size_t bytes = (size_t)mos.height * mos.width * planes;
+		const int short_write = fprintf(o, "P%d\n%u %u\n255\n", planes == 3 ? 6 : 5, mos.width, mos.height) < 0 || fwrite(mos.pixels, 1, bytes, o) != bytes;
+		if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--mosaic: writing %s failed: the picture is incomplete\n", name); code = 1; }
+	}
+	if (!code) {
+		snprintf(name, len, "%s_%s_mosaic.wld", base, tag);
+		o = fopen(name, "w");
+		if (!o) { fprintf(stderr, "--mosaic: could not open %s\n", name); code = 1; }
+		else {
+			const int short_write = fprintf(o, "%.17g\n0\n0\n%.17g\n%.17g\n%.17g\n", 1.0 / mos.sx, -1.0 / mos.sy, mos.lon_left + 0.5 / mos.sx, mos.lat_top - 0.5 / mos.sy) < 0;
+			if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--mosaic: writing %s failed: the world file is incomplete\n", name); code = 1; }
+		}
+	}
+	free(name);
+	if (!code) {
+		const double area = (double)mos.width * mos.height;
+		printf("%s: mosaic %s (%s): %u x %u at %u x %g px/deg; lat %.4f .. %.4f, lon %.4f .. %.4f; %u passes; first lines", base, tag,
+		       mos.blend == MDEMOD_MOSAIC_BEST ? "best" : "feather", mos.width, mos.height, mos.sx, mos.sy, mos.lat_top - mos.height / mos.sy, mos.lat_top, mos.lon_left,
+		       mos.lon_left + (double)mos.width / mos.sx, mos.n);
+		for (uint32_t k = 0; k < mos.n; k++) {
+			const double total = (double)mos.timing[k].date * 86400.0 + mos.utc0[k], day = floor(total / 86400.0), sec = total - day * 86400.0;
+			int y; unsigned m, d;
+			civil_from_days((int64_t)day, &y, &m, &d);
+			printf("%s %04d-%02u-%02uT%02d:%02d:%06.3fZ", k ? "," : "", y, m, d, (int)(sec / 3600.0), (int)(fmod(sec, 3600.0) / 60.0), fmod(sec, 60.0));
+		}
+		printf("; %.1f %% of pixels valid; %.1f %% seen by two or more passes\n", 100.0 * (double)mos.valid_pixels / area, 100.0 * (double)mos.overlap_pixels / area);
+	}
+	mdemod_mosaic_free(&mos);
+	return code;
+}
+
+/* --mosaic: the kept pictures of all files on one grid: the composite (--composite; auto on what the passes received together) or
+ * every channel that received a strip in any pass.  Frees what was kept.  0, or the exit status. */
+static int
+mosaic_files(const char *base, mdemod_image_result *kept, const struct stream_io *io, int n_files, const struct vcdu_req *req, int device)
+{
+	mdemod_mosaic_pass passes[MDEMOD_MOSAIC_MAX_PASSES];
+	uint32_t n = 0;
+	int got[3] = { 0, 0, 0 }, code = 0;
+	memset(passes, 0, sizeof passes);
+	for (int i = 0; i < n_files; i++) {
+		const mdemod_image_result *res = &kept[i];
+		const uint32_t rows = res->summary.rows;
+		int any = 0;
+		for (int k = 0; k < 3; k++)
+			for (uint64_t c = 0; c < (uint64_t)rows * MDEMOD_IMAGE_CELLS; c++)
+				if (res->filled[k][c]) { got[k] = any = 1; break; }
+		if (!any) { fprintf(stderr, "--mosaic: %s gave no picture: left out\n", io[i].in_name); continue; }
+		mdemod_mosaic_pass *p = &passes[n++];
+		p->tle_text = req->tle_text; p->norad = req->norad;
+		p->date = req->date_given ? req->map_date : MDEMOD_MOSAIC_DATE_AUTO;
+		for (int k = 0; k < 3; k++) { p->image[k] = res->image[k]; p->filled[k] = res->filled[k]; }
+		p->rows = rows; p->place = res->place; p->sinfo = res->sinfo; p->n_desc = res->n_packets;
+	}
+	char tag[16];
+	if (!n) { fprintf(stderr, "--mosaic: no pass gave a picture\n"); code = 1; }
+	else if (req->composite) {
+		uint32_t select[3] = { req->comp[0], req->comp[1], req->comp[2] };
+		int none = 0;
+		if (req->composite == 2) {
+			if (got[0] && got[1] && got[2]) { select[0] = 2; select[1] = 1; select[2] = 0; }
+			else if (got[0] && got[1]) { select[0] = 1; select[1] = 1; select[2] = 0; }
+			else none = 1;
+		}
+		if (none) printf("%s: no mosaic (--composite auto wants strips in all three channels, or in the first two)\n", base);
+		else {
+			snprintf(tag, sizeof tag, "%u%u%u", (unsigned)select[0] + 1, (unsigned)select[1] + 1, (unsigned)select[2] + 1);
+			code = mosaic_file(base, passes, n, req, select, 3, tag, device);
+		}
+	} else {
+		for (int k = 0; k < 3 && !code; k++) {
+			if (!got[k]) continue;
+			const uint32_t select[1] = { (uint32_t)k };
+			snprintf(tag, sizeof tag, "%u", (unsigned)req->apids[k]);
+			code = mosaic_file(base, passes, n, req, select, 1, tag, device);
+		}
+	}
+	for (int i = 0; i < n_files; i++) mdemod_image_free(&kept[i]);
+	return code;
+}
+
 /* --image: n VCDUs through the image layer, one PGM per active channel that received a strip beside the output file, one line.
  * 0, or the exit status. */
 static int
@@ -1070,7 +1203,8 @@ image_files(const char *s_name, const uint8_t *vcdu, const mdemod_rs_info *info,
 	}
 	if (!code && (req->rectify || req->composite)) code = picture_files(s_name, &res, req, device);
 	if (!code && req->map) code = map_files(s_name, &res, req, device);
-	mdemod_image_free(&res);
+	if (!code && req->keep) *req->keep = res;                                  /* (the mosaic frees it) */
+	else mdemod_image_free(&res);
 	return code;
 }
 
@@ -1200,8 +1334,9 @@ main(int argc, char **argv)
 	int use_fe = 0, decimation = 1;
 	double offset_hz = 0.0;
 	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0, want_vcdu = 0, want_diff = 0, want_skew = 0, want_int = 0, want_image = 0, apids_given = 0, geometry_given = 0, altitude_given = 0, map_opts_given = 0;
-	const char *map_fname = NULL;
+	const char *map_fname = NULL, *mosaic_base = NULL;
 	uint32_t map_norad = 0;
+	int mosaic_blend_given = 0;
 	struct vcdu_req vreq = { 0, 0, { 64, 65, 66 }, 0, 0, { 2, 1, 0 }, 0.0, 0.0 };
 	long int_delay = MDEMOD_IL_DEFAULT_BRANCH_DELAY;
 	double *auto_offsets = NULL;               /* --offset auto: the offset chosen for each file */
@@ -1303,6 +1438,13 @@ main(int argc, char **argv)
 			vreq.side = atoi(optarg);
 			map_opts_given = 1;
 			break;
+		case 0x20: mosaic_base = optarg; break;
+		case 0x21:
+			if (!strcmp(optarg, "feather")) vreq.mosaic_blend = MDEMOD_MOSAIC_FEATHER;
+			else if (!strcmp(optarg, "best")) vreq.mosaic_blend = MDEMOD_MOSAIC_BEST;
+			else { fprintf(stderr, "--mosaic-blend: feather or best\n"); return 1; }
+			mosaic_blend_given = 1;
+			break;
 		case 0x0b:
 			if (!strcmp(optarg, "auto")) { auto_offset = 1; use_fe = 1; break; }
 			auto_offset = 0;
@@ -1386,6 +1528,10 @@ main(int argc, char **argv)
 		        have_frames() ? "meteor_demod_amd_rs.h" : "meteor_demod_amd_frames.h");
 		return 1;
 	}
+	if (mosaic_base && !(have_mosaic() && have_map() && have_picture())) {
+		fprintf(stderr, "--mosaic: this library has no mosaic layer (built without include/meteor_demod_amd_mosaic.h's entries)\n");
+		return 1;
+	}
 	if (map_fname && !(have_map() && have_picture())) {
 		fprintf(stderr, "--map: this library has no map layer (built without include/meteor_demod_amd_map.h's entries)\n");
 		return 1;
@@ -1416,6 +1562,18 @@ main(int argc, char **argv)
 		fprintf(stderr, "--norad / --map-scale / --date / --time-offset / --scan-side: only with --map (they are its options)\n");
 		return 1;
 	}
+	if (mosaic_base && !(map_fname && want_image)) {
+		fprintf(stderr, "--mosaic: only with --map (and --image: it blends the maps of the input files)\n");
+		return 1;
+	}
+	if (mosaic_blend_given && !mosaic_base) {
+		fprintf(stderr, "--mosaic-blend: only with --mosaic (it is its option)\n");
+		return 1;
+	}
+	if (mosaic_base && n_files > MDEMOD_MOSAIC_MAX_PASSES) {
+		fprintf(stderr, "--mosaic: %d input files are more than a mosaic takes (1 .. 8 passes)\n", n_files);
+		return 1;
+	}
 	if (map_fname) {
 		/* the element set and the options are refused before anything is demodulated */
 		FILE *tf = fopen(map_fname, "rb");
@@ -1435,6 +1593,8 @@ main(int argc, char **argv)
 			return 1;
 		}
 		vreq.map = 1;
+		vreq.tle_text = text;
+		vreq.norad = map_norad;
 	}
 	if (geometry_given && !vreq.rectify && (altitude_given || !map_fname)) {
 		fprintf(stderr, "--altitude / --scan-angle: only with --rectify (they are the geometry it takes out)\n");
@@ -1683,7 +1843,19 @@ main(int argc, char **argv)
 	for (int d = 0; d < n_dev; d++) if (ws[d].rc > rc_all) rc_all = ws[d].rc;
 	/* (the workers closed their files through their own copies of the stream_io entries: nothing of the originals is open any more) */
 	for (int i = 0; i < n_files; i++) { io[i].in = NULL; io[i].out = NULL; }
+	/* (the frames, the pictures and the maps are made here, one file after the other, after the workers have joined: what --mosaic
+	   keeps of a file goes into that file's own entry, and nothing else touches it) */
+	mdemod_image_result kept[MDEMOD_MOSAIC_MAX_PASSES];
+	memset(kept, 0, sizeof kept);
 	if ((want_cadu || want_vcdu || want_image) && rc_all == 0)
-		for (int i = 0; i < n_files && rc_all == 0; i++) rc_all = cadu_file(io[i].out_name, devs[i % n_dev], want_cadu, &vreq, want_diff, want_skew, want_int ? (uint32_t)int_delay : 0);
+		for (int i = 0; i < n_files && rc_all == 0; i++) {
+			struct vcdu_req one = vreq;
+			if (mosaic_base) one.keep = &kept[i];
+			rc_all = cadu_file(io[i].out_name, devs[i % n_dev], want_cadu, &one, want_diff, want_skew, want_int ? (uint32_t)int_delay : 0);
+		}
+	if (mosaic_base) {
+		if (rc_all == 0) rc_all = mosaic_files(mosaic_base, kept, io, n_files, &vreq, devs[0]);
+		else for (int i = 0; i < n_files; i++) mdemod_image_free(&kept[i]);
+	}
 	LEAVE(rc_all);
 }

@@ -338,6 +338,104 @@ struct ModelBackend : MapBackend {
 
 } /* namespace */
 
+/* ---------------------------------------------------------------- what mdemod_map_grid and the mosaic layer's grid are made of */
+int
+map_check_pass(const char *who, const mdemod_map_tle *tle, const mdemod_map_timing *timing)
+{
+	const int rc = check_tle(who, tle);
+	return rc ? rc : check_timing(who, timing);
+}
+
+int
+map_check_lines(uint32_t lines)
+{
+	if (!lines || lines % 8) REFUSE("map: the picture has %u lines (a multiple of 8, at least 8)", lines);
+	if (lines / 8 > MDEMOD_MAP_MAX_ROWS) REFUSE("map: %u strip rows are more than a map takes (8192)", lines / 8);
+	return MDEMOD_OK;
+}
+
+int
+map_resolve_date(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, uint32_t lines, int32_t &date)
+{
+	return resolve_date(tle, tm, o, lines, date);
+}
+
+int
+map_swath_centre(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, uint32_t lines, double &lon_c)
+{
+	const Pass p = pass_of(tle, tm, o, date);
+	double lat_c;
+	if (!forward(p, (lines - 1) / 2.0, 783.5, lat_c, lon_c)) REFUSE("map: the middle of the picture does not see the Earth");
+	return MDEMOD_OK;
+}
+
+int
+map_swath_border(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, uint32_t lines, double lon_c, MapRange &range)
+{
+	const Pass p = pass_of(tle, tm, o, date);
+	int rc;
+	auto sample = [&](double y, double x) -> int {
+		double lat, lon;
+		if (!forward(p, y, x, lat, lon)) REFUSE("map: line %.0f, column %.0f on the border of the swath does not see the Earth (scan angle %g)", y, x, o.scan_deg);
+		if (fabs(lat) > MDEMOD_MAP_MAX_LAT)
+			REFUSE("map: line %.0f, column %.0f lies at %.2f degrees of latitude, beyond 85: a polar pass wants another projection", y, x, lat);
+		const double dl = wrap180(lon - lon_c);
+		range.lat_lo = std::min(range.lat_lo, lat); range.lat_hi = std::max(range.lat_hi, lat);
+		range.lon_lo = std::min(range.lon_lo, dl); range.lon_hi = std::max(range.lon_hi, dl);
+		return MDEMOD_OK;
+	};
+	for (uint32_t y = 0;; y = std::min(y + 8, lines - 1)) {
+		if ((rc = sample(y, 0.0)) || (rc = sample(y, PIC_LAST))) return rc;
+		if (y == lines - 1) break;
+	}
+	for (uint32_t x = 0;; x = std::min<uint32_t>(x + 16, PIC_LAST)) {
+		if ((rc = sample(0.0, x)) || (rc = sample(lines - 1, x))) return rc;
+		if (x == PIC_LAST) break;
+	}
+	return MDEMOD_OK;
+}
+
+int
+map_frame(const mdemod_map_opts &o, const MapRange &range, double lon_c, MapFrame &f)
+{
+	const double sy = o.px_per_deg, lat_mid = 0.5 * (range.lat_lo + range.lat_hi);
+	const double sx = std::max(1.0, floor(sy * cos(lat_mid * MAP_RAD) + 0.5));
+	const double lat_top = ceil(range.lat_hi * sy) / sy, left = floor((lon_c + range.lon_lo) * sx) / sx;
+	const double h = std::max(1.0, ceil((lat_top - range.lat_lo) * sy)), w = std::max(4.0, ceil(ceil((lon_c + range.lon_hi - left) * sx) / 4.0) * 4.0);
+	if (w > MDEMOD_MAP_MAX_WIDTH || h > MDEMOD_MAP_MAX_HEIGHT) {
+		const double fit = floor(sy * std::min(MDEMOD_MAP_MAX_WIDTH / (w + 8.0), MDEMOD_MAP_MAX_HEIGHT / (h + 2.0)));
+		REFUSE("map: %.0f x %.0f pixels at %g pixels per degree are more than a map takes (8192 x 16384): a scale of %.0f fits", w, h, sy, std::max(1.0, fit));
+	}
+	f.sy = sy; f.sx = sx; f.lat_top = lat_top; f.left = left;
+	f.width = static_cast<uint32_t>(w); f.height = static_cast<uint32_t>(h);
+	return MDEMOD_OK;
+}
+
+double
+map_frame_lon_left(const MapFrame &f)
+{
+	return f.left >= 180.0 ? f.left - 360.0 : f.left < -180.0 ? f.left + 360.0 : f.left;
+}
+
+void
+map_nodes_on(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, uint32_t lines, const MapFrame &f, int32_t *nodes)
+{
+	const Pass p = pass_of(tle, tm, o, date);
+	const Inverse inv(p, lines, o.scan_deg);
+	const uint32_t node_rows = map_node_count(f.height), node_cols = map_node_count(f.width);
+	for (uint32_t a = 0; a < node_rows; a++)
+		for (uint32_t b = 0; b < node_cols; b++) {
+			int32_t *node = nodes + 2 * (static_cast<size_t>(a) * node_cols + b);
+			double y, x;
+			node[0] = node[1] = MDEMOD_MAP_NO_NODE;
+			if (!inv.solve(f.lat_top - (MAP_STEP * a + 0.5) / f.sy, f.left + (MAP_STEP * b + 0.5) / f.sx, y, x)) continue;
+			const double X = floor(256.0 * x + 0.5), Y = floor(256.0 * y + 0.5);
+			if (!(fabs(X) < 2.0e9 && fabs(Y) < 2.0e9)) continue;
+			node[0] = static_cast<int32_t>(X);
+			node[1] = static_cast<int32_t>(Y);
+		}
+}
+
 int
 map_settings(const mdemod_map_opts *opts, mdemod_map_opts &out)
 {
@@ -591,65 +689,28 @@ mdemod_map_grid(const mdemod_map_tle *orbit, const mdemod_map_timing *timing, co
 try { MDEMOD_API_ENTER
 	mdemod_map_opts o;
 	int rc = map_settings(opts, o);
-	if (rc || (rc = check_tle("mdemod_map_grid", orbit)) || (rc = check_timing("mdemod_map_grid", timing))) return rc;
+	if (rc || (rc = map_check_pass("mdemod_map_grid", orbit, timing))) return rc;
 	if (!grid) REFUSE("mdemod_map_grid: the grid is needed");
 	memset(grid, 0, sizeof *grid);
-	if (!lines || lines % 8) REFUSE("map: the picture has %u lines (a multiple of 8, at least 8)", lines);
-	if (lines / 8 > MDEMOD_MAP_MAX_ROWS) REFUSE("map: %u strip rows are more than a map takes (8192)", lines / 8);
+	if ((rc = map_check_lines(lines))) return rc;
 	int32_t date;
-	if ((rc = resolve_date(*orbit, *timing, o, lines, date))) return rc;
-	const Pass p = pass_of(*orbit, *timing, o, date);
-	/* the border of the swath */
-	double lat_c, lon_c;
-	if (!forward(p, (lines - 1) / 2.0, 783.5, lat_c, lon_c)) REFUSE("map: the middle of the picture does not see the Earth");
-	double lat_lo = 1.0e9, lat_hi = -1.0e9, lon_lo = 1.0e9, lon_hi = -1.0e9;
-	auto sample = [&](double y, double x) -> int {
-		double lat, lon;
-		if (!forward(p, y, x, lat, lon)) REFUSE("map: line %.0f, column %.0f on the border of the swath does not see the Earth (scan angle %g)", y, x, o.scan_deg);
-		if (fabs(lat) > MDEMOD_MAP_MAX_LAT)
-			REFUSE("map: line %.0f, column %.0f lies at %.2f degrees of latitude, beyond 85: a polar pass wants another projection", y, x, lat);
-		const double dl = wrap180(lon - lon_c);
-		lat_lo = std::min(lat_lo, lat); lat_hi = std::max(lat_hi, lat);
-		lon_lo = std::min(lon_lo, dl); lon_hi = std::max(lon_hi, dl);
-		return MDEMOD_OK;
-	};
-	for (uint32_t y = 0;; y = std::min(y + 8, lines - 1)) {
-		if ((rc = sample(y, 0.0)) || (rc = sample(y, PIC_LAST))) return rc;
-		if (y == lines - 1) break;
-	}
-	for (uint32_t x = 0;; x = std::min<uint32_t>(x + 16, PIC_LAST)) {
-		if ((rc = sample(0.0, x)) || (rc = sample(lines - 1, x))) return rc;
-		if (x == PIC_LAST) break;
-	}
-	const double sy = o.px_per_deg, lat_mid = 0.5 * (lat_lo + lat_hi);
-	const double sx = std::max(1.0, floor(sy * cos(lat_mid * MAP_RAD) + 0.5));
-	const double lat_top = ceil(lat_hi * sy) / sy, left = floor((lon_c + lon_lo) * sx) / sx;
-	const double h = std::max(1.0, ceil((lat_top - lat_lo) * sy)), w = std::max(4.0, ceil(ceil((lon_c + lon_hi - left) * sx) / 4.0) * 4.0);
-	if (w > MDEMOD_MAP_MAX_WIDTH || h > MDEMOD_MAP_MAX_HEIGHT) {
-		const double fit = floor(sy * std::min(MDEMOD_MAP_MAX_WIDTH / (w + 8.0), MDEMOD_MAP_MAX_HEIGHT / (h + 2.0)));
-		REFUSE("map: %.0f x %.0f pixels at %g pixels per degree are more than a map takes (8192 x 16384): a scale of %.0f fits", w, h, sy, std::max(1.0, fit));
-	}
-	grid->width = static_cast<uint32_t>(w); grid->height = static_cast<uint32_t>(h);
-	grid->sx = static_cast<uint32_t>(sx); grid->sy = sy;
-	grid->lat_top = lat_top;
-	grid->lon_left = left >= 180.0 ? left - 360.0 : left < -180.0 ? left + 360.0 : left;
+	if ((rc = map_resolve_date(*orbit, *timing, o, lines, date))) return rc;
+	double lon_c;
+	MapRange range;
+	MapFrame f;
+	if ((rc = map_swath_centre(*orbit, *timing, o, date, lines, lon_c)) || (rc = map_swath_border(*orbit, *timing, o, date, lines, lon_c, range)) ||
+	    (rc = map_frame(o, range, lon_c, f)))
+		return rc;
+	grid->width = f.width; grid->height = f.height;
+	grid->sx = static_cast<uint32_t>(f.sx); grid->sy = f.sy;
+	grid->lat_top = f.lat_top;
+	grid->lon_left = map_frame_lon_left(f);
 	grid->date = date;
 	grid->node_rows = map_node_count(grid->height); grid->node_cols = map_node_count(grid->width);
 	const size_t count = static_cast<size_t>(grid->node_rows) * grid->node_cols;
 	grid->nodes = static_cast<int32_t *>(malloc(count * 2 * sizeof(int32_t)));
 	if (!grid->nodes) { memset(grid, 0, sizeof *grid); return MDEMOD_ERR_NOMEM; }
-	const Inverse inv(p, lines, o.scan_deg);
-	for (uint32_t a = 0; a < grid->node_rows; a++)
-		for (uint32_t b = 0; b < grid->node_cols; b++) {
-			int32_t *node = grid->nodes + 2 * (static_cast<size_t>(a) * grid->node_cols + b);
-			double y, x;
-			node[0] = node[1] = MDEMOD_MAP_NO_NODE;
-			if (!inv.solve(lat_top - (MAP_STEP * a + 0.5) / sy, left + (MAP_STEP * b + 0.5) / sx, y, x)) continue;
-			const double X = floor(256.0 * x + 0.5), Y = floor(256.0 * y + 0.5);
-			if (!(fabs(X) < 2.0e9 && fabs(Y) < 2.0e9)) continue;
-			node[0] = static_cast<int32_t>(X);
-			node[1] = static_cast<int32_t>(Y);
-		}
+	map_nodes_on(*orbit, *timing, o, date, lines, f, grid->nodes);
 	return MDEMOD_OK;
 } MDEMOD_API_CATCH
 

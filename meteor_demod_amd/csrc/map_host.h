@@ -40,6 +40,25 @@ int  map_check_compose(const char *who, const mdemod_map_tle *tle, const uint8_t
                        const mdemod_placement *place, const mdemod_strip_info *sinfo, uint64_t n_desc, const uint32_t *select, uint32_t planes,
                        mdemod_map_result *out);
 
+/* What mdemod_map_grid is made of, shared with the mosaic layer (csrc/mosaic_host.cpp): the swath's border samples with their
+ * refusals, the grid's frame from a range of latitudes and longitudes, and the nodes of a pass on a prescribed frame.  Longitudes
+ * of a range are relative to lon_c and wrapped to +-180; a fresh MapRange is empty and every border widens it. */
+struct MapRange { double lat_lo = 1.0e9, lat_hi = -1.0e9, lon_lo = 1.0e9, lon_hi = -1.0e9; };
+struct MapFrame { double sy, sx, lat_top, left; uint32_t width, height; };      /* left: lon_left before it is wrapped to -180 .. 180 */
+
+int  map_check_pass(const char *who, const mdemod_map_tle *tle, const mdemod_map_timing *timing);
+int  map_check_lines(uint32_t lines);
+int  map_resolve_date(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, uint32_t lines, int32_t &date);
+/* the longitude of pixel ((lines - 1) / 2, 783.5) */
+int  map_swath_centre(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, uint32_t lines, double &lon_c);
+int  map_swath_border(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, uint32_t lines, double lon_c,
+                      MapRange &range);
+int  map_frame(const mdemod_map_opts &o, const MapRange &range, double lon_c, MapFrame &f);
+double map_frame_lon_left(const MapFrame &f);
+/* nodes[map_node_count(f.height)][map_node_count(f.width)][2] of this pass */
+void map_nodes_on(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, uint32_t lines, const MapFrame &f,
+                  int32_t *nodes);
+
 extern "C" {
 
 /* the model of map_warp: host memory, the same rule */
