@@ -157,6 +157,11 @@ SIGNATURES = {
     "mdemod_selftest_turncode": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64)]),
     "mdemod_selftest_sinlut": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64)]),
     "mdemod_selftest_cabsf": (C.c_int, [C.c_void_p, C.c_uint64, _P(C.c_uint64), _P(C.c_uint64)]),
+    "mdemod_selftest_seam_match": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mdemod_selftest_assemble": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mdemod_selftest_window_power": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -138,6 +138,32 @@ int  mdemod_selftest_turncode(mdemod_ctx *ctx, uint64_t *n_checked, uint64_t *n_
 int  mdemod_selftest_cabsf(mdemod_ctx *ctx, uint64_t pairs, uint64_t *n_mismatch, uint64_t *n_fallback);   /* the short cabsf against the correctly rounded one on `pairs` pseudo-random pairs */
 int  mdemod_selftest_sinlut(mdemod_ctx *ctx, uint64_t *n_checked, uint64_t *n_mismatch);   /* the sine table in LDS against sincos.c's integer arithmetic: every turn code */
 
+
+/* ---- the stitcher's seam, copy and power kernels on tables a test makes up (csrc/recording.hip) ----------------------------
+ * Each entry builds the table the stitcher would have built and runs the stitcher's own launch code on it; none is on a hot
+ * path.  Offsets and counts are in symbols (int8 pairs) resp. samples, and are checked against the sizes given: a table that
+ * reaches past a buffer is refused (MDEMOD_ERR_PARAM, mdemod_last_error() names the argument), never launched. */
+
+/* Seam matches of n_pairs pairs: mode 0 tails (match_kernel), 1 rails (match_rails_kernel: no shift, shift_out is 0), 2 heads
+ * (match_heads_kernel).  Pair p compares a_cnt[p] symbols from a_off[p] of a_dev with b_cnt[p] symbols from b_off[p] of b_dev
+ * over K symbols; b_rot[p] quarter turns are applied to B in mode 0 and must be 0 in modes 1 and 2, whose kernels do not read
+ * it; force_weak[p] != 0 makes the pair weak whatever it holds.  The per-pair tables and the three results are host arrays.
+ * Refused: mode outside 0..2, K < 1, a non-zero b_rot in modes 1 and 2, NULL buffers or tables with n_pairs > 0.  No pairs: MDEMOD_OK. */
+int  mdemod_selftest_seam_match(int mode, const int8_t *a_dev, uint64_t a_symbols, const int8_t *b_dev, uint64_t b_symbols,
+                                const uint64_t *a_off, const uint32_t *a_cnt, const uint64_t *b_off, const uint32_t *b_cnt,
+                                const int32_t *b_rot, const int32_t *force_weak, uint32_t n_pairs, int K,
+                                int32_t *shift_out, int32_t *rot_out, int32_t *weak_out, void *hip_stream);
+/* The assembly copy of n_tiles tiles (host tables): keep[t] symbols from src_off[t] of src_dev, turned by rot[t] quarter turns,
+ * go to symbol dst[t] of out_dev; head_off[t] >= 0 puts that one symbol of src_dev, turned by head_rot[t], in front of them
+ * (-1: none).  Slices per tile as the stitcher picks them: min(64, max(1, 4096 / n_tiles)).  Returns when the copy is done. */
+int  mdemod_selftest_assemble(const int8_t *src_dev, uint64_t src_symbols, int8_t *out_dev, uint64_t out_symbols,
+                              const uint64_t *src_off, const uint32_t *keep, const int32_t *rot, const int64_t *head_off,
+                              const int32_t *head_rot, const uint64_t *dst, uint32_t n_tiles, void *hip_stream);
+/* Sample power (mean |z - mean|^2, the AGC seeds) of n_windows windows of lens[w] samples from starts[w] (host tables) of a
+ * recording of n_samples samples in the format params->bps; power_out_host: n_windows floats, 0 for an empty window. */
+int  mdemod_selftest_window_power(const mdemod_params *params, const void *iq_dev, uint64_t n_samples, const uint64_t *starts,
+                                  const uint32_t *lens, uint32_t n_windows, float *power_out_host, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,8 @@ namespace {
 struct TailPair {            /* what match_kernel compares for one tile */
 	const int8_t *a; uint32_t a_cnt;          /* A: reference demodulation (predecessor / pass 2) */
 	const int8_t *b; uint32_t b_cnt;          /* B: this tile's demodulation of the same samples  */
-	int32_t b_rot;                            /* quarter turns applied to B before comparing      */
+	int32_t b_rot;                            /* quarter turns applied to B before comparing: by match_kernel (tails)
+	                                             alone - the rails and heads kernels do not read it; the stitcher passes 0 */
 	int32_t force_weak;                       /* no overlap at all                                */
 };
 
@@ -188,7 +189,7 @@ match_heads_kernel(const TailPair *pairs, int K, int32_t *shift_out, int32_t *ro
 			for (int k = 1; k < 4; k++) if (sc4[k] > sc4[r]) r = k;
 			if (!have || sc4[r] > best) { best = sc4[r]; bs = shifts[c]; br = r; have = true; }
 		}
-		const bool weak = (best <= 0) || (4.0 * (double)best * (double)best < (double)t[6] * (double)t[7]);
+		const bool weak = (best <= 0) || (4.0 * (double)best * (double)best < (double)t[6] * (double)t[7]) || p.force_weak;
 		shift_out[blockIdx.x] = weak ? 0 : bs;
 		rot_out[blockIdx.x] = weak ? 0 : br;
 		weak_out[blockIdx.x] = weak ? 1 : 0;
@@ -362,8 +363,11 @@ clock_line_kernel(const void *iq, uint64_t n_samples, const uint64_t *starts, co
 	for (int l = 0; l < nline; l++) {
 		fl[l] = oqpsk ? fc2 + (l == 0 ? f_nom : -f_nom) : f_nom;
 		double sp = (double)nth * fl[l]; sp -= floor(sp);
-		float sn, cs;
-		sincospif(-2.0f * (float)sp, &sn, &cs); stp[l] = make_float2(cs, sn);
+		/* the step is applied 63 times between two settings from the phase: what its own phase is off by adds up to a slope,
+		   i.e. moves the line.  Rounded to float as a phase (up to 3e-8 turns) it moved lines by up to 2e-6 bin and the quality
+		   by 8e-7 of itself; taken in double and rounded as a rotation, a tenth of that (tests/test_gpu_stitch_kernels.py) */
+		double sn, cs;
+		sincospi(-2.0 * sp, &sn, &cs); stp[l] = make_float2((float)cs, (float)sn);
 		rot[l] = make_float2(1.0f, 0.0f);
 	}
 	for (int it = 0; it < nwin / nth; it++) {
@@ -571,6 +575,37 @@ run_match(MdmDevMem &m, const std::vector<TailPair> &pairs, int K, std::vector<i
 	HIP_TRY(hipMemcpyAsync(h.data(), d_out, 3 * T * sizeof(int32_t), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	shift.assign(h.begin(), h.begin() + T); rot.assign(h.begin() + T, h.begin() + 2 * T); weak.assign(h.begin() + 2 * T, h.end());
+	return MDEMOD_OK;
+}
+
+/* The copy of the tile table: upload, several blocks per tile when there are few tiles (so that the copy still fills the GPU),
+ * launch, wait.  What Stitcher::assemble() and the test entry mdemod_selftest_assemble both run. */
+int
+run_assemble(MdmDevMem &m, const std::vector<TileCopy> &copies, int8_t *out, hipStream_t st)
+{
+	const size_t T = copies.size();
+	if (T == 0) return MDEMOD_OK;
+	TileCopy *d_copies;
+	TRY(upload(m, copies, &d_copies, st));
+	const unsigned slices = static_cast<unsigned>(std::min<uint64_t>(64, std::max<uint64_t>(1, 4096 / T)));
+	hipLaunchKernelGGL(assemble_kernel, dim3(static_cast<unsigned>(T), slices), dim3(256), 0, st, d_copies, out);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(st));
+	return MDEMOD_OK;
+}
+
+/* Sample power of n_windows windows (device tables) of a recording in the format `bps`; asynchronous on st. */
+int
+run_window_power(int bps, const void *iq_dev, const uint64_t *d_starts, const uint32_t *d_lens, size_t n_windows, float *d_power, hipStream_t st)
+{
+	if (n_windows == 0) return MDEMOD_OK;
+	const dim3 grid(static_cast<unsigned>(n_windows));
+	switch (bps) {
+	case 16: hipLaunchKernelGGL(window_power_kernel<16>, grid, dim3(256), 0, st, iq_dev, d_starts, d_lens, d_power); break;
+	case 8:  hipLaunchKernelGGL(window_power_kernel<8>, grid, dim3(256), 0, st, iq_dev, d_starts, d_lens, d_power); break;
+	default: hipLaunchKernelGGL(window_power_kernel<32>, grid, dim3(256), 0, st, iq_dev, d_starts, d_lens, d_power); break;
+	}
+	HIP_TRY(hipGetLastError());
 	return MDEMOD_OK;
 }
 
@@ -1308,13 +1343,7 @@ struct Stitcher {
 			TRY(upload(mem, wl, &d_wl, st));
 			TRY(mem.alloc(&d_wp, ws.size()));
 			HIP_TRY(hipStreamSynchronize(st));
-			const dim3 grid(static_cast<unsigned>(ws.size()));
-			switch (params->bps) {
-			case 16: hipLaunchKernelGGL(window_power_kernel<16>, grid, dim3(256), 0, st, iq_dev, d_ws, d_wl, d_wp); break;
-			case 8:  hipLaunchKernelGGL(window_power_kernel<8>, grid, dim3(256), 0, st, iq_dev, d_ws, d_wl, d_wp); break;
-			default: hipLaunchKernelGGL(window_power_kernel<32>, grid, dim3(256), 0, st, iq_dev, d_ws, d_wl, d_wp); break;
-			}
-			HIP_TRY(hipGetLastError());
+			TRY(run_window_power(params->bps, iq_dev, d_ws, d_wl, ws.size(), d_wp, st));
 			std::vector<float> wp(ws.size());
 			HIP_TRY(hipMemcpyAsync(wp.data(), d_wp, wp.size() * sizeof(float), hipMemcpyDeviceToHost, st));
 			HIP_TRY(hipStreamSynchronize(st));
@@ -1654,13 +1683,7 @@ struct Stitcher {
 				break;
 			}
 		}
-		TileCopy *d_copies;
-		TRY(upload(mem, copies, &d_copies, st));
-		/* few tiles: several blocks per tile, so that the copy still fills the GPU */
-		const unsigned slices = static_cast<unsigned>(std::min<uint64_t>(64, std::max<uint64_t>(1, 4096 / T)));
-		hipLaunchKernelGGL(assemble_kernel, dim3(static_cast<unsigned>(T), slices), dim3(256), 0, st, d_copies, soft_dev);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(st));
+		TRY(run_assemble(mem, copies, soft_dev, st));
 		mark("assembled");
 		rep->n_symbols = out_pos;
 		rep->tiles_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_tiles).count();
@@ -1792,3 +1815,80 @@ try { MDEMOD_API_ENTER
 	mark("symbols copied out");
 	return MDEMOD_OK;
 } MDEMOD_API_CATCH
+
+/* ---- test entries (mdemod_internal_api.h): the production launches above on tables a test makes up -------------------------- */
+
+#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
+
+extern "C" int
+mdemod_selftest_seam_match(int mode, const int8_t *a_dev, uint64_t a_symbols, const int8_t *b_dev, uint64_t b_symbols,
+                           const uint64_t *a_off, const uint32_t *a_cnt, const uint64_t *b_off, const uint32_t *b_cnt,
+                           const int32_t *b_rot, const int32_t *force_weak, uint32_t n_pairs, int K,
+                           int32_t *shift_out, int32_t *rot_out, int32_t *weak_out, void *hip_stream)
+try { MDEMOD_API_ENTER
+	if (mode < 0 || mode > 2) REFUSE("mdemod_selftest_seam_match: mode = %d (0 tails, 1 rails, 2 heads)", mode);
+	if (K < 1) REFUSE("mdemod_selftest_seam_match: K = %d (at least 1)", K);
+	if (n_pairs == 0) return MDEMOD_OK;
+	if (!a_dev || !b_dev) REFUSE("mdemod_selftest_seam_match: %s is NULL with %u pairs", !a_dev ? "a_dev" : "b_dev", n_pairs);
+	if (!a_off || !a_cnt || !b_off || !b_cnt || !b_rot || !force_weak) REFUSE("mdemod_selftest_seam_match: a per-pair table (a_off, a_cnt, b_off, b_cnt, b_rot, force_weak) is NULL with %u pairs", n_pairs);
+	if (!shift_out || !rot_out || !weak_out) REFUSE("mdemod_selftest_seam_match: a result array (shift_out, rot_out, weak_out) is NULL with %u pairs", n_pairs);
+	std::vector<TailPair> pairs(n_pairs);
+	for (uint32_t i = 0; i < n_pairs; i++) {
+		if (mode != 0 && b_rot[i] != 0) REFUSE("mdemod_selftest_seam_match: b_rot[%u] = %d, but only mode 0 (match_kernel) applies b_rot", i, b_rot[i]);
+		if (a_off[i] > a_symbols || a_cnt[i] > a_symbols - a_off[i]) REFUSE("mdemod_selftest_seam_match: a_off[%u] + a_cnt[%u] lies past the %llu symbols of a_dev", i, i, (unsigned long long)a_symbols);
+		if (b_off[i] > b_symbols || b_cnt[i] > b_symbols - b_off[i]) REFUSE("mdemod_selftest_seam_match: b_off[%u] + b_cnt[%u] lies past the %llu symbols of b_dev", i, i, (unsigned long long)b_symbols);
+		pairs[i].a = a_dev + 2 * a_off[i]; pairs[i].a_cnt = a_cnt[i];
+		pairs[i].b = b_dev + 2 * b_off[i]; pairs[i].b_cnt = b_cnt[i];
+		pairs[i].b_rot = b_rot[i]; pairs[i].force_weak = force_weak[i];
+	}
+	MdmDevMem mem;
+	std::vector<int32_t> sh, ro, we;
+	TRY(run_match(mem, pairs, K, sh, ro, we, static_cast<hipStream_t>(hip_stream), mode));
+	for (uint32_t i = 0; i < n_pairs; i++) { shift_out[i] = sh[i]; rot_out[i] = ro[i]; weak_out[i] = we[i]; }
+	return MDEMOD_OK;
+} MDEMOD_API_CATCH
+
+extern "C" int
+mdemod_selftest_assemble(const int8_t *src_dev, uint64_t src_symbols, int8_t *out_dev, uint64_t out_symbols,
+                         const uint64_t *src_off, const uint32_t *keep, const int32_t *rot, const int64_t *head_off,
+                         const int32_t *head_rot, const uint64_t *dst, uint32_t n_tiles, void *hip_stream)
+try { MDEMOD_API_ENTER
+	if (n_tiles == 0) return MDEMOD_OK;
+	if (!src_dev || !out_dev) REFUSE("mdemod_selftest_assemble: %s is NULL with %u tiles", !src_dev ? "src_dev" : "out_dev", n_tiles);
+	if (!src_off || !keep || !rot || !head_off || !head_rot || !dst) REFUSE("mdemod_selftest_assemble: a per-tile table (src_off, keep, rot, head_off, head_rot, dst) is NULL with %u tiles", n_tiles);
+	std::vector<TileCopy> copies(n_tiles);
+	for (uint32_t i = 0; i < n_tiles; i++) {
+		const uint64_t room = static_cast<uint64_t>(keep[i]) + (head_off[i] >= 0 ? 1 : 0);
+		if (src_off[i] > src_symbols || keep[i] > src_symbols - src_off[i]) REFUSE("mdemod_selftest_assemble: src_off[%u] + keep[%u] lies past the %llu symbols of src_dev", i, i, (unsigned long long)src_symbols);
+		if (head_off[i] >= 0 && static_cast<uint64_t>(head_off[i]) >= src_symbols) REFUSE("mdemod_selftest_assemble: head_off[%u] lies past the %llu symbols of src_dev", i, (unsigned long long)src_symbols);
+		if (dst[i] > out_symbols || room > out_symbols - dst[i]) REFUSE("mdemod_selftest_assemble: dst[%u] + keep[%u] (+ head) lies past the %llu symbols of out_dev", i, i, (unsigned long long)out_symbols);
+		copies[i].src = src_dev + 2 * src_off[i]; copies[i].keep = keep[i]; copies[i].rot = rot[i];
+		copies[i].head = head_off[i] >= 0 ? src_dev + 2 * head_off[i] : nullptr; copies[i].head_rot = head_rot[i];
+		copies[i].dst = dst[i];
+	}
+	MdmDevMem mem;
+	return run_assemble(mem, copies, out_dev, static_cast<hipStream_t>(hip_stream));
+} MDEMOD_API_CATCH
+
+extern "C" int
+mdemod_selftest_window_power(const mdemod_params *params, const void *iq_dev, uint64_t n_samples, const uint64_t *starts,
+                             const uint32_t *lens, uint32_t n_windows, float *power_out_host, void *hip_stream)
+try { MDEMOD_API_ENTER
+	if (!params) REFUSE("mdemod_selftest_window_power: params is NULL");
+	if (params->bps != 8 && params->bps != 16 && params->bps != 32) REFUSE("mdemod_selftest_window_power: bps = %d (8, 16 or 32)", params->bps);
+	if (n_windows == 0) return MDEMOD_OK;
+	if (!iq_dev || !starts || !lens || !power_out_host) REFUSE("mdemod_selftest_window_power: iq_dev, starts, lens or power_out_host is NULL with %u windows", n_windows);
+	for (uint32_t w = 0; w < n_windows; w++)
+		if (starts[w] > n_samples || lens[w] > n_samples - starts[w]) REFUSE("mdemod_selftest_window_power: starts[%u] + lens[%u] lies past the %llu samples of iq_dev", w, w, (unsigned long long)n_samples);
+	hipStream_t st = static_cast<hipStream_t>(hip_stream);
+	MdmDevMem mem;
+	uint64_t *d_ws; uint32_t *d_wl; float *d_wp;
+	TRY(upload(mem, std::vector<uint64_t>(starts, starts + n_windows), &d_ws, st));
+	TRY(upload(mem, std::vector<uint32_t>(lens, lens + n_windows), &d_wl, st));
+	TRY(mem.alloc(&d_wp, n_windows));
+	TRY(run_window_power(params->bps, iq_dev, d_ws, d_wl, n_windows, d_wp, st));
+	HIP_TRY(hipMemcpyAsync(power_out_host, d_wp, n_windows * sizeof(float), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	return MDEMOD_OK;
+} MDEMOD_API_CATCH
+#undef REFUSE

@@ -78,6 +78,68 @@ def estimate_clock_native(cfg, iq, starts, window_samples: int, device: int = 0,
     return tf, qual
 
 
+def _host(a, dtype):
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def selftest_seam_match(mode: int, a, b, a_off, a_cnt, b_off, b_cnt, b_rot, force_weak, K: int, device: int = 0):
+    """``mdemod_selftest_seam_match``: the stitcher's seam matches (mode 0 tails, 1 rails, 2 heads) on int8 device tensors
+    [n, 2] (either may be None) and host tables per pair, offsets and counts in symbols: (shift, rot, weak) int32 arrays."""
+    import ctypes as C
+    import torch
+    from . import _capi
+    lib = _capi.lib()
+    for t in (a, b):
+        assert t is None or (t.is_cuda and t.dtype == torch.int8 and t.dim() == 2 and t.shape[1] == 2 and t.is_contiguous())
+    tabs = [_host(a_off, np.uint64), _host(a_cnt, np.uint32), _host(b_off, np.uint64), _host(b_cnt, np.uint32),
+            _host(b_rot, np.int32), _host(force_weak, np.int32)]
+    n = len(tabs[0])
+    assert all(len(t) == n for t in tabs)
+    out = [np.full(n, -99, dtype=np.int32) for _ in range(3)]
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _capi.check(lib.mdemod_selftest_seam_match(int(mode), ptr(a), 0 if a is None else int(a.shape[0]), ptr(b), 0 if b is None else int(b.shape[0]),
+                                               *[t.ctypes.data for t in tabs], n, int(K), *[o.ctypes.data for o in out],
+                                               C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "mdemod_selftest_seam_match")
+    return tuple(out)
+
+
+def selftest_assemble(src, out, src_off, keep, rot, head_off, head_rot, dst, device: int = 0):
+    """``mdemod_selftest_assemble``: the stitcher's copy of a tile table (host arrays, in symbols; head_off -1 = no head symbol)
+    from the int8 device tensor ``src`` [n, 2] into ``out`` [m, 2], in place."""
+    import ctypes as C
+    import torch
+    from . import _capi
+    lib = _capi.lib()
+    for t in (src, out):
+        assert t.is_cuda and t.dtype == torch.int8 and t.dim() == 2 and t.shape[1] == 2 and t.is_contiguous()
+    tabs = [_host(src_off, np.uint64), _host(keep, np.uint32), _host(rot, np.int32), _host(head_off, np.int64),
+            _host(head_rot, np.int32), _host(dst, np.uint64)]
+    n = len(tabs[0])
+    assert all(len(t) == n for t in tabs)
+    _capi.check(lib.mdemod_selftest_assemble(C.c_void_p(src.data_ptr()), int(src.shape[0]), C.c_void_p(out.data_ptr()), int(out.shape[0]),
+                                             *[t.ctypes.data for t in tabs], n,
+                                             C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "mdemod_selftest_assemble")
+
+
+def selftest_window_power(cfg, iq, starts, lens, device: int = 0):
+    """``mdemod_selftest_window_power``: sample power of windows (host tables, in samples) of the device tensor ``iq`` [n, 2] in
+    the format ``cfg.bps``, through the stitcher's launch: float32 array."""
+    import ctypes as C
+    import torch
+    from . import _capi
+    lib = _capi.lib()
+    assert iq.is_cuda and iq.dim() == 2 and iq.shape[1] == 2 and iq.is_contiguous()
+    assert iq.dtype == {8: torch.uint8, 16: torch.int16, 32: torch.float32}[cfg.bps]
+    p = cfg.to_c(1, device)
+    st, ln = _host(starts, np.uint64), _host(lens, np.uint32)
+    assert len(st) == len(ln)
+    out = np.full(len(st), np.nan, dtype=np.float32)
+    _capi.check(lib.mdemod_selftest_window_power(C.byref(p), C.c_void_p(iq.data_ptr()), int(iq.shape[0]), st.ctypes.data, ln.ctypes.data,
+                                                 len(st), out.ctypes.data, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                "mdemod_selftest_window_power")
+    return out
+
+
 def demodulate_recording_native(cfg, iq, tile_samples: int = 0, acquire_samples: int = AUTO, frame_samples: int = AUTO,
                                 settle_samples: int = AUTO, repair: bool = True, pilot_block: int = 65536,
                                 pilot_margin_symbols: int = AUTO, max_pilot_samples: int = 0xFFFFFFFFFFFFFFFF, match_symbols: int = 192,
