@@ -138,6 +138,7 @@ SIGNATURES = {
     "mdemod_clock_interp_magic": (C.c_uint32, [C.c_int32]),
     "mdemod_clock_table": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_int32), C.c_uint32]),
     "mdemod_plan_clock_table": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_uint32]),
+    "mdemod_plan_launch": (C.c_int, [C.c_void_p, _P(C.c_int32)]),
     "mdemod_device_count": (C.c_int, []),
     "mdemod_demodulate_recording_host": (C.c_int, [_P(MdemodParams), _P(MdemodRecordingOpts), C.c_void_p, C.c_uint64,
                                                    C.c_void_p, C.c_uint64, _P(MdemodRecordingReport)]),

@@ -50,6 +50,8 @@ def _run(cmd: list[str]) -> None:
 
 ROT_FLAGS = ["-fno-slp-vectorize", "-Wno-inline-asm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 ROTP_FLAGS = ["-fno-slp-vectorize", "-Wno-inline-asm"]
+# the source files that hold the demodulator's kernels; build() keeps the device assembly of each as lib/<stem>.gfx950.s
+DEMOD_KERNEL_UNITS = ("demod_kernel", "demod_kernel_rot", "demod_kernel_rotp", "demod_kernel_gat", "demod_kernel_lat")
 
 
 def _asm_limits() -> dict:
@@ -183,7 +185,9 @@ def build(force: bool = False, verbose: bool = False) -> dict[str, Path]:
             inc.write_text(text)
             headers = sorted(CSRC.glob("*.h")) + sorted((ROOT / "include").glob("*.h"))
     objs = []
-    asm_units = {"demod_kernel_rot": LIB / "demod_kernel_rot.gfx950.s", "demod_kernel_rotp": LIB / "demod_kernel_rotp.gfx950.s"}
+    # kept for every demodulator kernel file: the partition check reads the two assembly-owning ones, tests/demod_instances.py the
+    # entry labels of all five (one test-matrix row per compiled instance)
+    asm_units = {stem: LIB / (stem + ".gfx950.s") for stem in DEMOD_KERNEL_UNITS}
     checked = LIB / "asm_partition.ok"
     for src, stem, extra in units:
         obj = LIB / (stem + ".o")

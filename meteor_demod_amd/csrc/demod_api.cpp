@@ -76,6 +76,35 @@ wants_latency_kernel(const mdemod_ctx *ctx)
 	return ctx->params.n_streams <= most;
 }
 
+/* Which launch function a context goes to, and with which of the arguments that choose a compiled instance there: decided here once,
+ * for launch() below and for mdemod_plan_launch (host only: the test matrix of one row per instance reads it). */
+struct LaunchPick {
+	int kind;          /* MDEMOD_LAUNCH_*: lat, gat, roth, rot, rotp, v1 */
+	int geom;          /* roth / rotp: 0 = 129 taps (wide), 1 mid, 2 far */
+	int many_slides;   /* roth */
+	int compact;       /* rot */
+	int long_filter;   /* gat */
+};
+
+LaunchPick
+pick_launch(const mdemod_ctx *ctx)
+{
+	LaunchPick p = { MDEMOD_LAUNCH_V1, 0, 0, 0, 0 };
+	const int geom = ctx->tab.rw_mid ? 1 : (ctx->tab.rw_far ? 2 : 0);
+	/* Few streams: one stream per WAVE (demod_kernel_lat.hip) instead of one per lane.  A lane runs ~0.8 M symbols/s whatever
+	 * the batch, a wave 1.5 times that, and below a few thousand streams most of the GPU idles either way. */
+	if (wants_latency_kernel(ctx)) p.kind = MDEMOD_LAUNCH_LAT;
+	else if (ctx->tab.use_rw && ctx->tab.rw_gather) { p.kind = MDEMOD_LAUNCH_GAT; p.long_filter = ctx->tab.c.taps > 65 ? 1 : 0; }
+	else if (ctx->tab.use_rw && ctx->tab.rw_hyb) {
+		p.kind = MDEMOD_LAUNCH_ROTH; p.geom = geom;
+		p.many_slides = static_cast<double>(ctx->tab.osf) / (ctx->params.oqpsk ? 2.0 : 1.0) > 20.0 ? 1 : 0;
+	}
+	else if (ctx->tab.use_rw && ctx->use_rot) { p.kind = MDEMOD_LAUNCH_ROT; p.compact = ctx->tab.rw_std_compact ? 1 : 0; }
+	else if (ctx->tab.use_rw && ctx->tab.rw_compact4) { p.kind = MDEMOD_LAUNCH_ROTP; p.geom = geom; }
+	else if (ctx->tab.use_rw) p.kind = -1;           /* (cannot happen: every register-window plan is one of the v3 kernels above) */
+	return p;
+}
+
 int
 launch(mdemod_ctx *ctx, DemodLaunch &L, hipStream_t stream)
 {
@@ -86,25 +115,20 @@ launch(mdemod_ctx *ctx, DemodLaunch &L, hipStream_t stream)
 	L.ctab_floats = static_cast<uint32_t>(ctx->tab.ctab.size());
 	L.tanh_lut = ctx->d_lut;
 	L.c.clock_tab = ctx->d_clock_tab;
-	/* Few streams: one stream per WAVE (demod_kernel_lat.hip) instead of one per lane.  A lane runs ~0.8 M symbols/s whatever
-	 * the batch, a wave 1.5 times that, and below a few thousand streams most of the GPU idles either way. */
-	if (wants_latency_kernel(ctx)) {
+	const LaunchPick p = pick_launch(ctx);
+	switch (p.kind) {
+	case MDEMOD_LAUNCH_LAT:
 		HIP_TRY(mdemod_launch_demod_lat(L, ctx->params.bps, ctx->d_rrc, ctx->lat_ring, ctx->lat_span, ctx->tab.use_rw ? 1 : 0, ctx->lat_lds, stream));
-		return MDEMOD_OK;
-	}
-	if (ctx->tab.use_rw && ctx->tab.rw_gather)
-		HIP_TRY(mdemod_launch_demod_gat(L, ctx->params.bps, ctx->tab.c.taps > 65 ? 1 : 0, ctx->lds_bytes, stream));
-	else if (ctx->tab.use_rw && ctx->tab.rw_hyb)
-		HIP_TRY(mdemod_launch_demod_roth(L, ctx->tab.rw_mid ? 1 : (ctx->tab.rw_far ? 2 : 0),
-		                                 static_cast<double>(ctx->tab.osf) / (ctx->params.oqpsk ? 2.0 : 1.0) > 20.0 ? 1 : 0, ctx->lds_bytes, stream));
-	else if (ctx->tab.use_rw && ctx->use_rot)
-		HIP_TRY(mdemod_launch_demod_rot(L, ctx->params.bps, ctx->tab.rw_std_compact ? 1 : 0, ctx->lds_bytes, stream));
-	else if (ctx->tab.use_rw && ctx->tab.rw_compact4)
-		HIP_TRY(mdemod_launch_demod_rotp(L, ctx->params.bps, ctx->tab.rw_mid ? 1 : (ctx->tab.rw_far ? 2 : 0), ctx->lds_bytes, stream));
-	else if (ctx->tab.use_rw)
-		return MDEMOD_ERR_PARAM;                      /* (cannot happen: every register-window plan is one of the v3 kernels above) */
-	else
+		break;
+	case MDEMOD_LAUNCH_GAT:  HIP_TRY(mdemod_launch_demod_gat(L, ctx->params.bps, p.long_filter, ctx->lds_bytes, stream)); break;
+	case MDEMOD_LAUNCH_ROTH: HIP_TRY(mdemod_launch_demod_roth(L, p.geom, p.many_slides, ctx->lds_bytes, stream)); break;
+	case MDEMOD_LAUNCH_ROT:  HIP_TRY(mdemod_launch_demod_rot(L, ctx->params.bps, p.compact, ctx->lds_bytes, stream)); break;
+	case MDEMOD_LAUNCH_ROTP: HIP_TRY(mdemod_launch_demod_rotp(L, ctx->params.bps, p.geom, ctx->lds_bytes, stream)); break;
+	case MDEMOD_LAUNCH_V1:
 		HIP_TRY(mdemod_launch_demod(L, ctx->params.bps, ctx->block_threads, ctx->v1_global_table ? 1 : 0, ctx->lds_bytes, stream));
+		break;
+	default: return MDEMOD_ERR_PARAM;
+	}
 	return MDEMOD_OK;
 }
 
@@ -791,7 +815,8 @@ try { MDEMOD_API_ENTER
 	if (rc == MDEMOD_OK) {
 		snprintf(name, name_cap, "%s%s", mdemod_kernel_name(ctx), ctx->v1_global_table && !wants_latency_kernel(ctx) ? " [table in global memory]" : "");
 		if (lds_bytes) *lds_bytes = static_cast<uint32_t>(wants_latency_kernel(ctx) ? ctx->lat_lds : ctx->lds_bytes);
-		if (block_threads) *block_threads = static_cast<uint32_t>(ctx->tab.use_rw ? (ctx->tab.rw_wide ? MDEMOD_RW_WIDE_BLOCK : (ctx->tab.c.sin_lut ? MDEMOD_RW_LUT_BLOCK : MDEMOD_RW_BLOCK)) : ctx->block_threads);
+		/* (the latency kernel runs one wave per stream whatever the lane kernel of the configuration would take) */
+		if (block_threads) *block_threads = wants_latency_kernel(ctx) ? 64u : static_cast<uint32_t>(ctx->tab.use_rw ? (ctx->tab.rw_wide ? MDEMOD_RW_WIDE_BLOCK : (ctx->tab.c.sin_lut ? MDEMOD_RW_LUT_BLOCK : MDEMOD_RW_BLOCK)) : ctx->block_threads);
 	}
 	delete ctx;
 	return rc;
@@ -813,6 +838,31 @@ try { MDEMOD_API_ENTER
 			if (out && entries) memcpy(out, ctx->tab.clock_tab.data(), ctx->tab.clock_tab.size() * sizeof(int32_t));
 			rc = static_cast<int>(entries);
 		}
+	}
+	delete ctx;
+	return rc;
+} MDEMOD_API_CATCH
+
+int
+mdemod_plan_launch(const mdemod_params *params, int32_t out[MDEMOD_PLAN_LAUNCH_WORDS])
+try { MDEMOD_API_ENTER
+	if (!params || !out || params->n_streams == 0) return MDEMOD_ERR_PARAM;
+	mdemod_ctx *ctx = new (std::nothrow) mdemod_ctx();
+	if (!ctx) return MDEMOD_ERR_NOMEM;
+	ctx->params = *params;
+	ctx->pipe = nullptr;
+	int rc = plan_context(ctx);
+	if (rc == MDEMOD_OK) {
+		const LaunchPick p = pick_launch(ctx);
+		const DemodConsts &c = ctx->tab.c;
+		const bool lat = p.kind == MDEMOD_LAUNCH_LAT, v1 = p.kind == MDEMOD_LAUNCH_V1;
+		const int32_t v[MDEMOD_PLAN_LAUNCH_WORDS] = {
+			p.kind, params->bps, c.oqpsk ? 1 : 0, c.step_safe, c.sin_lut ? 1 : 0, ctx->tab.clock_tab.empty() ? 0 : 1,
+			p.geom, p.many_slides, p.compact, p.long_filter,
+			v1 ? ctx->block_threads : 0, v1 && ctx->v1_global_table ? 1 : 0, v1 ? c.win_granules : 0,
+			lat && ctx->tab.use_rw ? 1 : 0, 0, 0 };
+		memcpy(out, v, sizeof(v));
+		if (p.kind < 0) rc = MDEMOD_ERR_PARAM;
 	}
 	delete ctx;
 	return rc;

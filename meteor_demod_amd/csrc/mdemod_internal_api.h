@@ -117,6 +117,18 @@ int  mdemod_clock_table(int32_t interp, int32_t k_safe, int32_t *out, uint32_t c
  * one of the rotating-window ones, or a table that does not fit the LDS next to the rest. */
 int  mdemod_plan_clock_table(const mdemod_params *params, int32_t *out, uint32_t cap_entries);
 
+/* What the launch code would take for `params` - host only, read only: the launch function mdemod_create's plan leads to and every
+ * argument and constant by which that function picks ONE compiled kernel instance (the planner's name and block size do not tell
+ * sample formats, modulations or compiled-in step counts apart).  out[]: 0 the launch function (MDEMOD_LAUNCH_*), 1 bps, 2 oqpsk,
+ * 3 the symbol clock's blind steps (step_safe), 4 sine table in LDS, 5 a clock position table is handed over, 6 geometry of the
+ * packed / hybrid windows (0 = 129 taps, 1 mid, 2 far), 7 many slides (hybrid), 8 compact coefficient rows (std window), 9 long
+ * filter (gather), 10 threads per block of the v1 ring kernel, 11 its table in global memory, 12 its window granules, 13 float
+ * history (latency kernel on a register-window context), 14-15 zero.  Words that the launch function does not read are 0 where
+ * they would differ between contexts of the same instance (10-13). */
+enum { MDEMOD_LAUNCH_LAT = 0, MDEMOD_LAUNCH_GAT = 1, MDEMOD_LAUNCH_ROTH = 2, MDEMOD_LAUNCH_ROT = 3, MDEMOD_LAUNCH_ROTP = 4, MDEMOD_LAUNCH_V1 = 5 };
+#define MDEMOD_PLAN_LAUNCH_WORDS 16
+int  mdemod_plan_launch(const mdemod_params *params, int32_t out[MDEMOD_PLAN_LAUNCH_WORDS]);
+
 /* RRC polyphase table as filter_init_rrc lays it out (filter.c:18-22):
  * interp*taps floats, bank-major.  Returns number of floats, or <0. */
 int  mdemod_get_rrc_table(const mdemod_ctx *ctx, float *out, uint32_t cap);

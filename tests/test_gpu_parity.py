@@ -310,6 +310,8 @@ def test_wide_window_batch_chained(name, gpu_device, monkeypatch):
             ost = O.OracleStream(cfg)
             want = ost.run(iqs[i])[0]
             assert np.array_equal(np.concatenate(parts[i]), want), (name, i)
+            # (16 050 samples are fewer symbols than a cold lock takes from 460 kS/s up: for most rows `locked` is 0 == 0 here.  The
+            # locked half of the loop, lock events and relock on these kernels: tests/test_gpu_demod_instances.py)
             assert np.float32(st[i].pll_freq) == np.float32(ost.state.pll_freq) and st[i].locked == ost.state.locked
             assert st[i].n_samples == sum(blocks)
 
