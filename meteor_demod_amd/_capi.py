@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 from pathlib import Path
 
+import numpy as np
+
 LIB_DIR = Path(__file__).resolve().parent / "lib"
 LIB_PATH = LIB_DIR / "libmeteor_demod_amd.so"
 import os as _os
@@ -195,15 +197,33 @@ def lib() -> C.CDLL:
             raise RuntimeError(
                 f"{LIB_PATH} is missing: build the HIP extension first "
                 "(python -m meteor_demod_amd.build). There is no CPU fallback.")
-        handle = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in SIGNATURES.items():
-            if _os.environ.get("MDEMOD_LIB_PATH") and not hasattr(handle, name):
-                continue                                   # an older build of the library on A/B duty (tools/ab4.py): newer entries are simply absent
+        # an older build of the library on A/B duty (tools/ab4.py): newer entries of the main table are simply absent
+        _lib = _typed(C.CDLL(str(LIB_PATH)), SIGNATURES, missing_ok=bool(_os.environ.get("MDEMOD_LIB_PATH")))
+    return _lib
+
+
+def _typed(handle: C.CDLL, *tables: dict, missing_ok: bool = False) -> C.CDLL:
+    """`handle` with restype and argtypes set for every entry of the given name -> (restype, argtypes) tables."""
+    for table in tables:
+        for name, (res, args) in table.items():
+            if missing_ok and not hasattr(handle, name):
+                continue
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
-        _lib = handle
-    return _lib
+    return handle
+
+
+def bind(*tables: dict) -> C.CDLL:
+    """The handle of ``lib()`` with a layer's own tables applied as well: what every layer module's cached ``lib()`` is."""
+    return _typed(lib(), *tables)
+
+
+def take_bytes(ptr, count: int, dtype=np.uint8) -> np.ndarray:
+    """A copy of `count` elements of `dtype` that a result struct of the library points to (a NULL or empty one gives an empty
+    array): taken before the struct's ``*_free`` entry releases them."""
+    dtype = np.dtype(dtype)
+    return np.frombuffer(C.string_at(ptr, count * dtype.itemsize), dtype=dtype).copy() if count else np.zeros(0, dtype=dtype)
 
 
 def strerror(code: int) -> str:

@@ -1,13 +1,12 @@
 /*
  * map.hip — the map layer on the GPU (include/meteor_demod_amd_map.h): map_warp, and the public entries around it.  The
- * specification is the host model of csrc/map_host.cpp.
+ * specification is the host model of csrc/map_host.cpp over csrc/warp_model.h.
  *
  * map_warp: a block of 256 threads makes a tile of 32 x 32 output pixels (64 x 16 and 128 x 8 were measured beside it and were
  *   slower); a thread makes 4 neighbouring pixels of one line.  Four pixels at a multiple of 4 lie in one cell of the node grid, so
- *   the thread reads the cell's four nodes once (through the cache: a copy of the tile's nodes in LDS gained nothing) and
- *   interpolates them down the cell's column first:
- *   L = (16 - p) X00 + p X10 and R = (16 - p) X01 + p X11, after which the numerator of pixel q is 16 L + q (R - L) + 128, an
- *   addition per pixel; all of it in 64 bits, since a node may hold any int32.  The taps are byte loads straight through the cache:
+ *   the thread reads the cell's four nodes once (through the cache: a copy of the tile's nodes in LDS gained nothing).  From the
+ *   nodes to the source bytes the thread's work is csrc/warp_device.h, shared with mosaic_blend: the interpolation, the taps, the
+ *   mask rule and the packing.  The taps are byte loads straight through the cache:
  *   the source of a tile is a slanted quadrilateral whose bounding box depends on the nodes, neighbouring threads read neighbouring
  *   bytes, and every source byte is used by the one or two tiles it falls into (profiles/map.md has what was tried, with times).
  *   The tables (planes x 256 bytes) sit in LDS.  The result is 4 x planes bytes packed into 3 dwords (colour) or 1 (grey), and
@@ -20,6 +19,7 @@
 
 #include "map_host.h"
 #include "hip_host.h"
+#include "warp_device.h"
 
 #define MAP_THREADS 256
 #define MAP_TILE_W  32                      /* the tile is MAP_TILE_W x (4 * MAP_THREADS / MAP_TILE_W) pixels */
@@ -36,13 +36,6 @@ struct MapWarp {
 	uint32_t width, height, rows, node_cols;
 };
 
-__device__ __forceinline__ bool
-map_tap_rule(bool fa, bool fb, uint32_t a, uint32_t b, uint32_t f, uint32_t &v)
-{
-	v = fa && fb ? (a * (256u - f) + b * f + 128u) >> 8 : fa ? a : b;
-	return fa || fb;
-}
-
 template <int PLANES>
 __global__ void __launch_bounds__(MAP_THREADS)
 map_warp(MapWarp a)
@@ -55,65 +48,37 @@ map_warp(MapWarp a)
 	__syncthreads();
 	if (i >= a.height || j0 >= a.width) return;
 	const uint8_t *lut = reinterpret_cast<const uint8_t *>(tab);
-	int32_t n[4][2];                                        /* 00, 10 (one down), 01 (one to the right), 11 */
-	const int32_t *g = a.nodes + 2 * (static_cast<size_t>(i / MAP_STEP) * a.node_cols + j0 / MAP_STEP);
-#pragma unroll
-	for (int w = 0; w < 2; w++) { n[0][w] = g[w]; n[1][w] = g[2 * a.node_cols + w]; n[2][w] = g[2 + w]; n[3][w] = g[2 * a.node_cols + 2 + w]; }
-	bool there = true;
-#pragma unroll
-	for (int c = 0; c < 4; c++) there = there && !(n[c][0] == MDEMOD_MAP_NO_NODE && n[c][1] == MDEMOD_MAP_NO_NODE);
-	const int64_t p = i & 15u, q0 = j0 & 15u;
-	const int64_t lx = (16 - p) * n[0][0] + p * n[1][0], rx = (16 - p) * n[2][0] + p * n[3][0];
-	const int64_t ly = (16 - p) * n[0][1] + p * n[1][1], ry = (16 - p) * n[2][1] + p * n[3][1];
-	int64_t nx = 16 * lx + q0 * (rx - lx) + 128, ny = 16 * ly + q0 * (ry - ly) + 128;
+	WarpQuad c;
+	const bool there = warp_quad(a.nodes + 2 * (static_cast<size_t>(i / MAP_STEP) * a.node_cols + j0 / MAP_STEP), a.node_cols, i, j0, c);
 	const int64_t y_top = (8ll * a.rows - 1) * 256;
 	const uint32_t last_line = 8 * a.rows - 1;
 	uint32_t bytes[4 * PLANES], seen = 0;
 #pragma unroll
 	for (int k = 0; k < 4; k++) {
-		const int64_t X = nx >> 8, Y = ny >> 8;
-		nx += rx - lx;
-		ny += ry - ly;
+		const int64_t X = c.nx >> 8, Y = c.ny >> 8;
+		c.nx += c.dx;
+		c.ny += c.dy;
 #pragma unroll
 		for (int pl = 0; pl < PLANES; pl++) bytes[PLANES * k + pl] = 0;
 		if (!(there && X >= 0 && X <= MAP_X_TOP && Y >= 0 && Y <= y_top)) continue;
-		const uint32_t ix = static_cast<uint32_t>(X) >> 8, fx = static_cast<uint32_t>(X) & 255u, ix2 = min(ix + 1, static_cast<uint32_t>(PIC_LAST));
-		const uint32_t iy = static_cast<uint32_t>(Y) >> 8, fy = static_cast<uint32_t>(Y) & 255u, iy2 = min(iy + 1, last_line);
-		const uint32_t c0 = ix / PIC_CELL_W, c1 = ix2 / PIC_CELL_W, r0 = (iy >> 3) * PIC_CELLS, r1 = (iy2 >> 3) * PIC_CELLS;
-		const uint32_t o0 = iy * PIC_SRC_W, o1 = iy2 * PIC_SRC_W;
-		const bool one_cell = c0 == c1 && r0 == r1;
+		const WarpTaps taps = warp_taps(static_cast<uint32_t>(X), static_cast<uint32_t>(Y), last_line);
 #pragma unroll
 		for (int pl = 0; pl < PLANES; pl++) {
-			const uint8_t *src = a.image[pl], *cells = a.filled[pl];
-			uint32_t v0, v1, v;
-			/* the four taps lie in one cell but at a cell's last column or a strip row's last line: one mask byte then */
-			bool f00 = cells[r0 + c0] != 0, f01 = f00, f10 = f00, f11 = f00;
-			if (!one_cell) { f01 = cells[r0 + c1] != 0; f10 = cells[r1 + c0] != 0; f11 = cells[r1 + c1] != 0; }
-			const bool l0 = map_tap_rule(f00, f01, src[o0 + ix], src[o0 + ix2], fx, v0);
-			const bool l1 = map_tap_rule(f10, f11, src[o1 + ix], src[o1 + ix2], fx, v1);
-			if (map_tap_rule(l0, l1, v0, v1, fy, v)) {
+			uint32_t v;
+			if (warp_sample(a.image[pl], a.filled[pl], taps, v)) {
 				bytes[PLANES * k + pl] = lut[256 * pl + v];
 				seen |= (1u << pl) << (8 * k);
 			}
 		}
 	}
 	const size_t at = static_cast<size_t>(i) * a.width + j0;
-	uint32_t *to = reinterpret_cast<uint32_t *>(a.out + at * PLANES);
-#pragma unroll
-	for (int d = 0; d < PLANES; d++) to[d] = bytes[4 * d] | (bytes[4 * d + 1] << 8) | (bytes[4 * d + 2] << 16) | (bytes[4 * d + 3] << 24);
+	warp_store<PLANES>(a.out, at, bytes);
 	if (a.valid) *reinterpret_cast<uint32_t *>(a.valid + at) = seen;
 }
 
 namespace {
 
 #define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
-bool
-map_intersect(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-	return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
 
 int
 warp_run(const uint8_t *const image[3], const uint8_t *const filled[3], uint32_t rows, const uint32_t *select, uint32_t planes, const uint8_t *lut_dev,
@@ -149,12 +114,12 @@ warp_entry(const char *who, const uint8_t *const image_dev[3], const uint8_t *co
 	const uint64_t node_bytes = 8ull * map_node_count(height) * map_node_count(width), lut_bytes = 256 * planes;
 	const void *outs[2] = { out_dev, valid_dev };
 	const uint64_t out_sizes[2] = { out_bytes, valid_bytes };
-	bool hit = map_intersect(out_dev, out_bytes, valid_dev, valid_bytes);
+	bool hit = mdm_ranges_intersect(out_dev, out_bytes, valid_dev, valid_bytes);
 	for (int k = 0; k < 2; k++) {
-		hit = hit || map_intersect(outs[k], out_sizes[k], lut_dev, lut_bytes) || map_intersect(outs[k], out_sizes[k], nodes_dev, node_bytes);
+		hit = hit || mdm_ranges_intersect(outs[k], out_sizes[k], lut_dev, lut_bytes) || mdm_ranges_intersect(outs[k], out_sizes[k], nodes_dev, node_bytes);
 		for (uint32_t p = 0; p < planes; p++)
-			hit = hit || map_intersect(outs[k], out_sizes[k], image_dev[select[p]], rows * PIC_LINE_BYTES) ||
-			      map_intersect(outs[k], out_sizes[k], filled_dev[select[p]], static_cast<uint64_t>(rows) * PIC_CELLS);
+			hit = hit || mdm_ranges_intersect(outs[k], out_sizes[k], image_dev[select[p]], rows * PIC_LINE_BYTES) ||
+			      mdm_ranges_intersect(outs[k], out_sizes[k], filled_dev[select[p]], static_cast<uint64_t>(rows) * PIC_CELLS);
 	}
 	if (hit) REFUSE("%s: the outputs and the inputs intersect (the blocks of one launch would read what others write)", who);
 	if ((rc = mdm_select_device(device))) return rc;

@@ -1,8 +1,8 @@
 /*
  * map_host.cpp — host side of the map layer (include/meteor_demod_amd_map.h): the TLE parser, the circular J2 orbit, the time fit,
  * the forward function (pixel to latitude / longitude), the grid with its nodes (the forward function inverted), the bands of the
- * whole-map entry, and the host model of the kernel of csrc/map.hip (mdemod_map_model_*: plain loops over the header's text).
- * Free of the GPU runtime.
+ * whole-map entry, and the host model of the kernel of csrc/map.hip (mdemod_map_model_*: a plain loop over the warp's model, which
+ * csrc/warp_model.h holds once for this layer and the mosaic layer).  Free of the GPU runtime.
  *
  * The inverse.  A ground point G is seen from line time t exactly when it lies in the scan plane of that moment, the plane through
  * the satellite spanned by r and h: G . v(t) = 0 in Earth-fixed coordinates (r . v = 0).  That is one equation in one unknown, and
@@ -20,6 +20,7 @@
 
 #include "map_host.h"
 #include "mdemod_internal_api.h"
+#include "warp_model.h"
 
 #define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
 
@@ -265,53 +266,24 @@ struct Inverse {
 	}
 };
 
-/* the tap rule: 0 when neither counts */
-inline bool
-tap_rule(bool fa, bool fb, uint32_t a, uint32_t b, uint32_t f, uint32_t &v)
-{
-	if (fa && fb) v = (a * (256u - f) + b * f + 128u) >> 8;
-	else if (fa) v = a;
-	else if (fb) v = b;
-	else return false;
-	return true;
-}
-
 void
 model_warp(const uint8_t *const image[3], const uint8_t *const filled[3], uint32_t rows, const uint32_t *select, uint32_t planes, const uint8_t *lut,
            const int32_t *nodes, uint32_t width, uint32_t height, uint8_t *out, uint8_t *valid)
 {
 	const uint32_t nc = map_node_count(width);
-	const int64_t y_top = (8ll * rows - 1) * 256;
 	for (uint32_t i = 0; i < height; i++)
 		for (uint32_t j = 0; j < width; j++) {
 			uint8_t *px = out + (static_cast<size_t>(i) * width + j) * planes;
 			uint8_t seen = 0;
+			int64_t X, Y;
 			memset(px, 0, planes);
-			const int32_t *n00 = nodes + 2 * (static_cast<size_t>(i >> 4) * nc + (j >> 4)), *n10 = n00 + 2 * nc, *n01 = n00 + 2, *n11 = n10 + 2;
-			bool there = true;
-			for (const int32_t *n : { n00, n10, n01, n11 }) there = there && !(n[0] == MDEMOD_MAP_NO_NODE && n[1] == MDEMOD_MAP_NO_NODE);
-			if (there) {
-				const int64_t p = i & 15, q = j & 15;
-				const int64_t w00 = (16 - p) * (16 - q), w10 = p * (16 - q), w01 = (16 - p) * q, w11 = p * q;
-				const int64_t X = (w00 * n00[0] + w10 * n10[0] + w01 * n01[0] + w11 * n11[0] + 128) >> 8;
-				const int64_t Y = (w00 * n00[1] + w10 * n10[1] + w01 * n01[1] + w11 * n11[1] + 128) >> 8;
-				if (X >= 0 && X <= MAP_X_TOP && Y >= 0 && Y <= y_top) {
-					const uint32_t ix = static_cast<uint32_t>(X >> 8), fx = static_cast<uint32_t>(X & 255), ix2 = ix + 1 < PIC_LAST ? ix + 1 : PIC_LAST;
-					const uint32_t iy = static_cast<uint32_t>(Y >> 8), fy = static_cast<uint32_t>(Y & 255), iy2 = iy + 1 < 8 * rows - 1 ? iy + 1 : 8 * rows - 1;
-					for (uint32_t pl = 0; pl < planes; pl++) {
-						const uint8_t *src = image[select[pl]], *cells = filled[select[pl]];
-						uint32_t v0 = 0, v1 = 0, v = 0;
-						const bool c0 = tap_rule(cells[(iy / 8) * PIC_CELLS + ix / PIC_CELL_W] != 0, cells[(iy / 8) * PIC_CELLS + ix2 / PIC_CELL_W] != 0,
-						                         src[static_cast<size_t>(iy) * PIC_SRC_W + ix], src[static_cast<size_t>(iy) * PIC_SRC_W + ix2], fx, v0);
-						const bool c1 = tap_rule(cells[(iy2 / 8) * PIC_CELLS + ix / PIC_CELL_W] != 0, cells[(iy2 / 8) * PIC_CELLS + ix2 / PIC_CELL_W] != 0,
-						                         src[static_cast<size_t>(iy2) * PIC_SRC_W + ix], src[static_cast<size_t>(iy2) * PIC_SRC_W + ix2], fx, v1);
-						if (tap_rule(c0, c1, v0, v1, fy, v)) {
-							px[pl] = lut[256 * pl + v];
-							seen |= static_cast<uint8_t>(1u << pl);
-						}
-					}
+			if (warp_model_point(nodes, nc, rows, i, j, X, Y))
+				for (uint32_t pl = 0; pl < planes; pl++) {
+					uint32_t v;
+					if (!warp_model_value(image[select[pl]], filled[select[pl]], rows, X, Y, v)) continue;
+					px[pl] = lut[256 * pl + v];
+					seen |= static_cast<uint8_t>(1u << pl);
 				}
-			}
 			if (valid) valid[static_cast<size_t>(i) * width + j] = seen;
 		}
 }

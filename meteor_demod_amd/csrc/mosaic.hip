@@ -1,12 +1,12 @@
 /*
  * mosaic.hip — the mosaic layer on the GPU (include/meteor_demod_amd_mosaic.h): mosaic_blend, and the public entries around it.
- * The specification is the host model of csrc/mosaic_host.cpp.
+ * The specification is the host model of csrc/mosaic_host.cpp over csrc/warp_model.h.
  *
  * mosaic_blend: one launch makes the finished bytes; there is no accumulator image in memory and no atomic.  The geometry is
  *   map_warp's (csrc/map.hip): a block of 256 threads makes a tile of 32 x 32 output pixels, a thread makes 4 neighbouring pixels
- *   of one line, which lie in one cell of the node grid.  The loop over the passes runs inside the thread: per pass the cell's four
- *   nodes are read once and interpolated down the cell's column first, all in 64 bits (a node may hold any int32); the taps are byte
- *   loads through the cache.  Per pixel and plane the thread keeps two words, the weighted sum and the sum of weights (FEATHER) or
+ *   of one line, which lie in one cell of the node grid.  The loop over the passes runs inside the thread, and per pass the way from
+ *   the cell's nodes to the source bytes is map_warp's own code (csrc/warp_device.h: interpolation, taps, mask rule, packing), not
+ *   a copy of it.  Per pixel and plane the thread keeps two words, the weighted sum and the sum of weights (FEATHER) or
  *   the byte with its pass and the weight of the best pass so far (BEST).  The pass descriptors travel by value in the kernel arguments and are
  *   indexed by the loop counter, which is uniform: scalar loads.  All passes' tables sit in LDS (8 x planes x 256 bytes, of which
  *   n x planes x 256 are filled).  A tile of 32 x 32 pixels touches 3 x 3 nodes: every wave looks at the nine nodes of each pass
@@ -22,6 +22,7 @@
 
 #include "mosaic_host.h"
 #include "hip_host.h"
+#include "warp_device.h"
 
 #define MOSAIC_THREADS 256
 #define MOSAIC_TILE_W  32                      /* the tile is MOSAIC_TILE_W x (4 * MOSAIC_THREADS / MOSAIC_TILE_W) pixels */
@@ -43,13 +44,6 @@ struct MosaicBlend {
 	uint8_t *cover;
 	uint32_t width, height, node_rows, node_cols, n, blend;
 };
-
-__device__ __forceinline__ bool
-mosaic_tap_rule(bool fa, bool fb, uint32_t a, uint32_t b, uint32_t f, uint32_t &v)
-{
-	v = fa && fb ? (a * (256u - f) + b * f + 128u) >> 8 : fa ? a : b;
-	return fa || fb;
-}
 
 /* n / d for n < 2^21 and 1 <= d <= 6272: the float quotient is off by far less than 1, so one step either way makes it exact */
 __device__ __forceinline__ uint32_t
@@ -78,10 +72,7 @@ mosaic_blend(MosaicBlend a)
 			bool there = false;
 			if (a.pass[k].rows) {
 				for (uint32_t w = t; w < PLANES * 64; w += MOSAIC_THREADS) tab[k * PLANES * 64 + w] = reinterpret_cast<const uint32_t *>(a.pass[k].lut)[w];
-				if (mine) {
-					const int32_t *g = a.pass[k].nodes + 2 * (static_cast<size_t>(nr) * a.node_cols + nc);
-					there = !(g[0] == MDEMOD_MOSAIC_NO_NODE && g[1] == MDEMOD_MOSAIC_NO_NODE);
-				}
+				if (mine) there = !warp_no_node(a.pass[k].nodes + 2 * (static_cast<size_t>(nr) * a.node_cols + nc));
 			}
 			if (__ballot(there)) alive |= 1u << k;
 		}
@@ -91,7 +82,6 @@ mosaic_blend(MosaicBlend a)
 	if (i >= a.height || j0 >= a.width) return;
 	const uint8_t *lut = reinterpret_cast<const uint8_t *>(tab);
 	const bool feather = a.blend == MDEMOD_MOSAIC_FEATHER;
-	const int64_t p = i & 15u, q0 = j0 & 15u;
 	const size_t cell = 2 * (static_cast<size_t>(i / MAP_STEP) * a.node_cols + j0 / MAP_STEP);
 	uint32_t sum[4 * PLANES], weight[4 * PLANES], from = 0;
 #pragma unroll
@@ -99,42 +89,24 @@ mosaic_blend(MosaicBlend a)
 	for (uint32_t k = 0; k < a.n; k++) {
 		if (!((alive >> k) & 1u)) continue;
 		const MosaicPass &ps = a.pass[k];
-		int32_t n[4][2];                                        /* 00, 10 (one down), 01 (one to the right), 11 */
-		const int32_t *g = ps.nodes + cell;
-#pragma unroll
-		for (int w = 0; w < 2; w++) { n[0][w] = g[w]; n[1][w] = g[2 * a.node_cols + w]; n[2][w] = g[2 + w]; n[3][w] = g[2 * a.node_cols + 2 + w]; }
-		bool there = true;
-#pragma unroll
-		for (int c = 0; c < 4; c++) there = there && !(n[c][0] == MDEMOD_MOSAIC_NO_NODE && n[c][1] == MDEMOD_MOSAIC_NO_NODE);
-		if (!there) continue;
-		const int64_t lx = (16 - p) * n[0][0] + p * n[1][0], rx = (16 - p) * n[2][0] + p * n[3][0];
-		const int64_t ly = (16 - p) * n[0][1] + p * n[1][1], ry = (16 - p) * n[2][1] + p * n[3][1];
-		int64_t nx = 16 * lx + q0 * (rx - lx) + 128, ny = 16 * ly + q0 * (ry - ly) + 128;
+		WarpQuad c;
+		if (!warp_quad(ps.nodes + cell, a.node_cols, i, j0, c)) continue;
 		const int64_t y_top = (8ll * ps.rows - 1) * 256;
 		const uint32_t last_line = 8 * ps.rows - 1;
 		const uint8_t *tables = lut + k * PLANES * 256;
 #pragma unroll
 		for (int px = 0; px < 4; px++) {
-			const int64_t X = nx >> 8, Y = ny >> 8;
-			nx += rx - lx;
-			ny += ry - ly;
+			const int64_t X = c.nx >> 8, Y = c.ny >> 8;
+			c.nx += c.dx;
+			c.ny += c.dy;
 			if (!(X >= 0 && X <= MAP_X_TOP && Y >= 0 && Y <= y_top)) continue;
 			const uint32_t x = static_cast<uint32_t>(X), y = static_cast<uint32_t>(Y);
 			const uint32_t e = min(min(x, static_cast<uint32_t>(MAP_X_TOP) - x), min(y, static_cast<uint32_t>(y_top) - y)), w = 1u + (e >> 8);
-			const uint32_t ix = x >> 8, fx = x & 255u, ix2 = min(ix + 1, static_cast<uint32_t>(PIC_LAST));
-			const uint32_t iy = y >> 8, fy = y & 255u, iy2 = min(iy + 1, last_line);
-			const uint32_t c0 = ix / PIC_CELL_W, c1 = ix2 / PIC_CELL_W, r0 = (iy >> 3) * PIC_CELLS, r1 = (iy2 >> 3) * PIC_CELLS;
-			const uint32_t o0 = iy * PIC_SRC_W, o1 = iy2 * PIC_SRC_W;
-			const bool one_cell = c0 == c1 && r0 == r1;
+			const WarpTaps taps = warp_taps(x, y, last_line);
 #pragma unroll
 			for (int pl = 0; pl < PLANES; pl++) {
-				const uint8_t *src = ps.image[pl], *cells = ps.filled[pl];
-				uint32_t v0, v1, v;
-				bool f00 = cells[r0 + c0] != 0, f01 = f00, f10 = f00, f11 = f00;
-				if (!one_cell) { f01 = cells[r0 + c1] != 0; f10 = cells[r1 + c0] != 0; f11 = cells[r1 + c1] != 0; }
-				const bool l0 = mosaic_tap_rule(f00, f01, src[o0 + ix], src[o0 + ix2], fx, v0);
-				const bool l1 = mosaic_tap_rule(f10, f11, src[o1 + ix], src[o1 + ix2], fx, v1);
-				if (mosaic_tap_rule(l0, l1, v0, v1, fy, v)) {
+				uint32_t v;
+				if (warp_sample(ps.image[pl], ps.filled[pl], taps, v)) {
 					const uint32_t b = tables[256 * pl + v];
 					uint32_t &s = sum[PLANES * px + pl], &d = weight[PLANES * px + pl];
 					if (feather) { s += w * b; d += w; from |= (1u << k) << (8 * px); }
@@ -154,9 +126,7 @@ mosaic_blend(MosaicBlend a)
 			if (d && !feather) from |= (1u << (s >> 8)) << (8 * px);
 		}
 	const size_t at = static_cast<size_t>(i) * a.width + j0;
-	uint32_t *to = reinterpret_cast<uint32_t *>(a.out + at * PLANES);
-#pragma unroll
-	for (int d = 0; d < PLANES; d++) to[d] = bytes[4 * d] | (bytes[4 * d + 1] << 8) | (bytes[4 * d + 2] << 16) | (bytes[4 * d + 3] << 24);
+	warp_store<PLANES>(a.out, at, bytes);
 	if (a.valid) *reinterpret_cast<uint32_t *>(a.valid + at) = seen;
 	if (a.cover) *reinterpret_cast<uint32_t *>(a.cover + at) = from;
 }
@@ -164,13 +134,6 @@ mosaic_blend(MosaicBlend a)
 namespace {
 
 #define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
-bool
-mosaic_intersect(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-	return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
 
 /* nodes of every pass: from the band's first node row on */
 int
@@ -214,16 +177,16 @@ blend_entry(const char *who, const mdemod_mosaic_source *sources, uint32_t n, co
 	const void *outs[3] = { out_dev, valid_dev, cover_dev };
 	const uint64_t out_sizes[3] = { area * planes, valid_dev ? area : 0, cover_dev ? area : 0 };
 	const uint64_t node_bytes = 8ull * map_node_count(height) * map_node_count(width), lut_bytes = 256 * planes;
-	bool hit = mosaic_intersect(out_dev, out_sizes[0], valid_dev, out_sizes[1]) || mosaic_intersect(out_dev, out_sizes[0], cover_dev, out_sizes[2]) ||
-	           mosaic_intersect(valid_dev, out_sizes[1], cover_dev, out_sizes[2]);
+	bool hit = mdm_ranges_intersect(out_dev, out_sizes[0], valid_dev, out_sizes[1]) || mdm_ranges_intersect(out_dev, out_sizes[0], cover_dev, out_sizes[2]) ||
+	           mdm_ranges_intersect(valid_dev, out_sizes[1], cover_dev, out_sizes[2]);
 	for (int o = 0; o < 3; o++)
 		for (uint32_t k = 0; k < n; k++) {
 			const mdemod_mosaic_source &s = sources[k];
 			if (!s.rows) continue;
-			hit = hit || mosaic_intersect(outs[o], out_sizes[o], s.lut, lut_bytes) || mosaic_intersect(outs[o], out_sizes[o], s.nodes, node_bytes);
+			hit = hit || mdm_ranges_intersect(outs[o], out_sizes[o], s.lut, lut_bytes) || mdm_ranges_intersect(outs[o], out_sizes[o], s.nodes, node_bytes);
 			for (uint32_t p = 0; p < planes; p++)
-				hit = hit || mosaic_intersect(outs[o], out_sizes[o], s.image[select[p]], s.rows * PIC_LINE_BYTES) ||
-				      mosaic_intersect(outs[o], out_sizes[o], s.filled[select[p]], static_cast<uint64_t>(s.rows) * PIC_CELLS);
+				hit = hit || mdm_ranges_intersect(outs[o], out_sizes[o], s.image[select[p]], s.rows * PIC_LINE_BYTES) ||
+				      mdm_ranges_intersect(outs[o], out_sizes[o], s.filled[select[p]], static_cast<uint64_t>(s.rows) * PIC_CELLS);
 		}
 	if (hit) REFUSE("%s: the outputs and the inputs intersect (the blocks of one launch would read what others write)", who);
 	if ((rc = mdm_select_device(device))) return rc;

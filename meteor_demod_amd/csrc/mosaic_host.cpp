@@ -1,8 +1,8 @@
 /*
  * mosaic_host.cpp — host side of the mosaic layer (include/meteor_demod_amd_mosaic.h): the common grid of several passes out of the
  * map layer's pieces (csrc/map_host.h: border samples, frame, nodes on a prescribed frame), the stretch tables, the bands of the
- * whole-mosaic entry, and the host model of the kernel of csrc/mosaic.hip (mdemod_mosaic_model_*: plain loops over the header's
- * text).  Free of the GPU runtime.
+ * whole-mosaic entry, and the host model of the kernel of csrc/mosaic.hip (mdemod_mosaic_model_*: the blend as a plain loop over
+ * the warp's model, which is the map layer's: csrc/warp_model.h).  Free of the GPU runtime.
  */
 #include <cstdlib>
 #include <cstring>
@@ -10,52 +10,11 @@
 
 #include "mosaic_host.h"
 #include "mdemod_internal_api.h"
+#include "warp_model.h"
 
 #define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
 
 namespace {
-
-/* the tap rule: false when neither counts */
-inline bool
-tap_rule(bool fa, bool fb, uint32_t a, uint32_t b, uint32_t f, uint32_t &v)
-{
-	if (fa && fb) v = (a * (256u - f) + b * f + 128u) >> 8;
-	else if (fa) v = a;
-	else if (fb) v = b;
-	else return false;
-	return true;
-}
-
-/* the warp rule of pass `s` at output pixel (i, j): false where the pass is empty */
-bool
-warp_point(const mdemod_mosaic_source &s, uint32_t nc, uint32_t i, uint32_t j, int64_t &X, int64_t &Y)
-{
-	if (!s.rows) return false;
-	const int32_t *n00 = s.nodes + 2 * (static_cast<size_t>(i >> 4) * nc + (j >> 4)), *n10 = n00 + 2 * nc, *n01 = n00 + 2, *n11 = n10 + 2;
-	for (const int32_t *n : { n00, n10, n01, n11 })
-		if (n[0] == MDEMOD_MOSAIC_NO_NODE && n[1] == MDEMOD_MOSAIC_NO_NODE) return false;
-	const int64_t p = i & 15, q = j & 15;
-	const int64_t w00 = (16 - p) * (16 - q), w10 = p * (16 - q), w01 = (16 - p) * q, w11 = p * q;
-	X = (w00 * n00[0] + w10 * n10[0] + w01 * n01[0] + w11 * n11[0] + 128) >> 8;
-	Y = (w00 * n00[1] + w10 * n10[1] + w01 * n01[1] + w11 * n11[1] + 128) >> 8;
-	return X >= 0 && X <= MAP_X_TOP && Y >= 0 && Y <= (8ll * s.rows - 1) * 256;
-}
-
-/* the tap rule on one slot of pass `s` at (X, Y) */
-bool
-tap_value(const mdemod_mosaic_source &s, uint32_t slot, int64_t X, int64_t Y, uint32_t &v)
-{
-	const uint32_t last = 8 * s.rows - 1;
-	const uint32_t ix = static_cast<uint32_t>(X >> 8), fx = static_cast<uint32_t>(X & 255), ix2 = ix + 1 < PIC_LAST ? ix + 1 : PIC_LAST;
-	const uint32_t iy = static_cast<uint32_t>(Y >> 8), fy = static_cast<uint32_t>(Y & 255), iy2 = iy + 1 < last ? iy + 1 : last;
-	const uint8_t *src = s.image[slot], *cells = s.filled[slot];
-	uint32_t v0 = 0, v1 = 0;
-	const bool c0 = tap_rule(cells[(iy / 8) * PIC_CELLS + ix / PIC_CELL_W] != 0, cells[(iy / 8) * PIC_CELLS + ix2 / PIC_CELL_W] != 0,
-	                         src[static_cast<size_t>(iy) * PIC_SRC_W + ix], src[static_cast<size_t>(iy) * PIC_SRC_W + ix2], fx, v0);
-	const bool c1 = tap_rule(cells[(iy2 / 8) * PIC_CELLS + ix / PIC_CELL_W] != 0, cells[(iy2 / 8) * PIC_CELLS + ix2 / PIC_CELL_W] != 0,
-	                         src[static_cast<size_t>(iy2) * PIC_SRC_W + ix], src[static_cast<size_t>(iy2) * PIC_SRC_W + ix2], fx, v1);
-	return tap_rule(c0, c1, v0, v1, fy, v);
-}
 
 void
 model_blend(const mdemod_mosaic_source *sources, uint32_t n, const uint32_t *select, uint32_t planes, uint32_t blend, uint32_t width, uint32_t height,
@@ -68,17 +27,18 @@ model_blend(const mdemod_mosaic_source *sources, uint32_t n, const uint32_t *sel
 			uint32_t best[3] = { 0, 0, 0 };
 			uint8_t seen = 0, from = 0;
 			for (uint32_t k = 0; k < n; k++) {
+				const mdemod_mosaic_source &s = sources[k];
 				int64_t X, Y;
-				if (!warp_point(sources[k], nc, i, j, X, Y)) continue;
-				const int64_t y_top = (8ll * sources[k].rows - 1) * 256;
+				if (!s.rows || !warp_model_point(s.nodes, nc, s.rows, i, j, X, Y)) continue;       /* an empty pass, or nothing of it here */
+				const int64_t y_top = (8ll * s.rows - 1) * 256;
 				int64_t e = X < MAP_X_TOP - X ? X : MAP_X_TOP - X;
 				e = Y < e ? Y : e;
 				e = y_top - Y < e ? y_top - Y : e;
 				const uint64_t w = 1 + static_cast<uint64_t>(e >> 8);
 				for (uint32_t p = 0; p < planes; p++) {
 					uint32_t v;
-					if (!tap_value(sources[k], select[p], X, Y, v)) continue;
-					const uint64_t b = sources[k].lut[256 * p + v];
+					if (!warp_model_value(s.image[select[p]], s.filled[select[p]], s.rows, X, Y, v)) continue;
+					const uint64_t b = s.lut[256 * p + v];
 					if (blend == MDEMOD_MOSAIC_FEATHER) { sum[p] += w * b; weight[p] += w; from |= static_cast<uint8_t>(1u << k); }
 					else if (w > weight[p]) { sum[p] = b; weight[p] = w; best[p] = k; }
 					seen |= static_cast<uint8_t>(1u << p);

@@ -12,6 +12,9 @@
 #define MOSAIC_MAX      MDEMOD_MOSAIC_MAX_PASSES
 #define MOSAIC_W_TOP    784                        /* the largest weight */
 
+/* the warp is the map layer's, on the device (csrc/warp_device.h) and in the model (csrc/warp_model.h): one word for "no node" */
+static_assert(MDEMOD_MOSAIC_NO_NODE == MDEMOD_MAP_NO_NODE, "a pass's nodes are tested against the map layer's MDEMOD_MAP_NO_NODE");
+
 /* opts (NULL: the defaults) checked and completed (piece_lines 0 -> 1024); MDEMOD_ERR_PARAM with a text otherwise */
 int  mosaic_settings(const mdemod_mosaic_opts *opts, mdemod_mosaic_opts &out);
 

@@ -130,19 +130,13 @@ namespace {
 
 #define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
 
-bool
-pic_intersect(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-	return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
-
 /* an output against every input slot that is there */
 bool
 pic_hits_slots(const void *out, uint64_t out_bytes, const uint8_t *const image[3], const uint8_t *const filled[3], uint32_t rows)
 {
 	for (int s = 0; s < 3; s++)
-		if (pic_intersect(out, out_bytes, image[s], rows * PIC_LINE_BYTES) || pic_intersect(out, out_bytes, filled[s], static_cast<uint64_t>(rows) * PIC_CELLS))
+		if (mdm_ranges_intersect(out, out_bytes, image[s], rows * PIC_LINE_BYTES) ||
+		    mdm_ranges_intersect(out, out_bytes, filled[s], static_cast<uint64_t>(rows) * PIC_CELLS))
 			return true;
 	return false;
 }
@@ -274,9 +268,9 @@ try { MDEMOD_API_ENTER
 	const uint8_t *img[3] = { nullptr, nullptr, nullptr }, *fil[3] = { nullptr, nullptr, nullptr };
 	for (uint32_t p = 0; p < planes; p++) { img[select[p]] = image_dev[select[p]]; fil[select[p]] = filled_dev[select[p]]; }
 	if (pic_hits_slots(out_dev, out_bytes, img, fil, rows) || pic_hits_slots(valid_dev, valid_bytes, img, fil, rows) ||
-	    pic_intersect(out_dev, out_bytes, lut_dev, 256 * planes) || pic_intersect(out_dev, out_bytes, map_dev, 4ull * width) ||
-	    pic_intersect(valid_dev, valid_bytes, lut_dev, 256 * planes) || pic_intersect(valid_dev, valid_bytes, map_dev, 4ull * width) ||
-	    pic_intersect(out_dev, out_bytes, valid_dev, valid_bytes))
+	    mdm_ranges_intersect(out_dev, out_bytes, lut_dev, 256 * planes) || mdm_ranges_intersect(out_dev, out_bytes, map_dev, 4ull * width) ||
+	    mdm_ranges_intersect(valid_dev, valid_bytes, lut_dev, 256 * planes) || mdm_ranges_intersect(valid_dev, valid_bytes, map_dev, 4ull * width) ||
+	    mdm_ranges_intersect(out_dev, out_bytes, valid_dev, valid_bytes))
 		REFUSE("mdemod_picture_render_device: the outputs and the inputs intersect (the blocks of one launch would read what others write)");
 	if ((rc = mdm_select_device(device))) return rc;
 	return render_run(image_dev, filled_dev, rows, select, planes, lut_dev, map_dev, width, out_dev, valid_dev, static_cast<hipStream_t>(hip_stream));

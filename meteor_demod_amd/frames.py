@@ -13,6 +13,7 @@ entries are called.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from dataclasses import dataclass
 
 import numpy as np
@@ -85,20 +86,10 @@ LINK_MODEL_SIGNATURES = {
                                                   C.c_uint64, _P(C.c_uint64)]),
 }
 
-_lib = None
-
-
+@functools.cache
 def lib() -> C.CDLL:
     """The product library with the frame layer's entries typed (the same handle as ``_capi.lib()``)."""
-    global _lib
-    if _lib is None:
-        h = _capi.lib()
-        for name, (res, args) in {**SIGNATURES, **MODEL_SIGNATURES, **LINK_SIGNATURES, **LINK_MODEL_SIGNATURES}.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = h
-    return _lib
+    return _capi.bind(SIGNATURES, MODEL_SIGNATURES, LINK_SIGNATURES, LINK_MODEL_SIGNATURES)
 
 
 @dataclass

@@ -8,6 +8,7 @@ the reference's, bit for bit.  This module keeps its own binding table: the main
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 from dataclasses import dataclass, replace
 
@@ -45,20 +46,10 @@ SIGNATURES = {
                                                       C.c_uint64, C.c_void_p, C.c_uint64, _P(MdemodRecordingReport)]),
 }
 
-_lib = None
-
-
+@functools.cache
 def lib() -> C.CDLL:
     """The product library with the front end's entries typed (the same handle as ``_capi.lib()``)."""
-    global _lib
-    if _lib is None:
-        h = _capi.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = h
-    return _lib
+    return _capi.bind(SIGNATURES)
 
 
 @dataclass

@@ -9,12 +9,13 @@ the host model of csrc/image_host.cpp, the kernels' specification.  This module 
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from dataclasses import dataclass, field
 
 import numpy as np
 
 from . import _capi
-from ._capi import check
+from ._capi import check, take_bytes
 
 VCDU_BYTES, ZONE, STRIP_BYTES, WIDTH, CELLS, OVERLAP, MAX_PER_FRAME = 892, 882, 896, 1568, 14, 76, 126
 NOT_IMAGE, BAD_HEADER, TRUNCATED, OUTSIDE = 1, 2, 4, 8
@@ -60,20 +61,10 @@ MODEL_SIGNATURES = {
     "mdemod_image_model_host": (C.c_int, [_P(MdemodImageOpts), C.c_void_p, C.c_void_p, C.c_uint64, _P(MdemodImageResult)]),
 }
 
-_lib = None
-
-
+@functools.cache
 def lib() -> C.CDLL:
     """The product library with this layer's entries typed (the same handle as ``_capi.lib()``)."""
-    global _lib
-    if _lib is None:
-        h = _capi.lib()
-        for name, (res, args) in {**SIGNATURES, **MODEL_SIGNATURES}.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = h
-    return _lib
+    return _capi.bind(SIGNATURES, MODEL_SIGNATURES)
 
 
 def make_opts(**opts) -> MdemodImageOpts:
@@ -260,13 +251,12 @@ def _take(res: MdemodImageResult, o: MdemodImageOpts) -> Result:
     """A C result into arrays of our own; the C side's memory goes back."""
     try:
         m, rows = int(res.n_packets), int(res.summary.rows)
-        grab = lambda p, count, dt: np.frombuffer(C.string_at(p, count * np.dtype(dt).itemsize), dtype=dt).copy() if count else np.zeros(0, dtype=dt)
-        out = Result(grab(res.desc, m, DESC_DTYPE), grab(res.sinfo, m, SINFO_DTYPE), grab(res.strips, m * STRIP_BYTES, np.uint8).reshape(-1, 8, 112),
-                     grab(res.place, m, PLACE_DTYPE), _summary(res.summary))
+        out = Result(take_bytes(res.desc, m, DESC_DTYPE), take_bytes(res.sinfo, m, SINFO_DTYPE), take_bytes(res.strips, m * STRIP_BYTES).reshape(-1, 8, 112),
+                     take_bytes(res.place, m, PLACE_DTYPE), _summary(res.summary))
         for k in range(3):
             a = int(o.apids[k])
-            out.images[a] = grab(res.image[k], rows * 8 * WIDTH, np.uint8).reshape(8 * rows, WIDTH)
-            out.filled[a] = grab(res.filled[k], rows * CELLS, np.uint8).reshape(rows, CELLS).astype(bool)
+            out.images[a] = take_bytes(res.image[k], rows * 8 * WIDTH).reshape(8 * rows, WIDTH)
+            out.filled[a] = take_bytes(res.filled[k], rows * CELLS).reshape(rows, CELLS).astype(bool)
         return out
     finally:
         lib().mdemod_image_free(C.byref(res))

@@ -10,6 +10,7 @@ csrc/interleave_host.cpp, the kernels' specification.  This module keeps its own
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from dataclasses import dataclass
 
 import numpy as np
@@ -53,20 +54,10 @@ MODEL_SIGNATURES = {
     "mdemod_il_model_deinterleave": (C.c_int, [_P(MdemodIlOpts), C.c_void_p, C.c_uint64, _P(MdemodIlSegment), C.c_uint64, C.c_uint64, C.c_void_p]),
 }
 
-_lib = None
-
-
+@functools.cache
 def lib() -> C.CDLL:
     """The product library with this layer's entries typed (the same handle as ``_capi.lib()``)."""
-    global _lib
-    if _lib is None:
-        h = _capi.lib()
-        for name, (res, args) in {**SIGNATURES, **MODEL_SIGNATURES}.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = h
-    return _lib
+    return _capi.bind(SIGNATURES, MODEL_SIGNATURES)
 
 
 @dataclass

@@ -4,18 +4,20 @@
 forward function (pixel to latitude / longitude), ``grid`` makes the latitude / longitude grid with its nodes, ``warp`` resamples
 the slots through the nodes on the GPU (device tensors in and out); ``compose`` chains them for numpy arrays (through
 ``mdemod_map_compose_host``, in bands) and ``image_to_map`` takes what ``image.vcdu_to_image`` returns.  ``model_*`` is the host
-model of csrc/map_host.cpp, the kernel's specification.  This module keeps its own binding table, as ``picture.py`` does.
+model of csrc/map_host.cpp over csrc/warp_model.h, the kernel's specification.  This module keeps its own binding tables, as every
+layer's does; ``_capi.bind`` applies them.
 """
 from __future__ import annotations
 
 import ctypes as C
 import datetime
+import functools
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _capi, picture
-from ._capi import check
+from ._capi import check, take_bytes
 from .picture import _SLOTS, _dev_slots, _host_slots, _select, composite_select
 
 NODE_STEP = 16
@@ -73,20 +75,12 @@ MODEL_SIGNATURES = {
 PLACEMENT = np.dtype([("channel", "<i4"), ("row", "<u4"), ("cell", "<u4"), ("reserved", "<u4")])
 STRIP_INFO = np.dtype([("mcus", "u1"), ("q", "u1"), ("mcun", "u1"), ("flags", "u1"), ("day", "<u2"), ("us", "<u2"), ("ms", "<u4"), ("bits_used", "<u4")])
 
-_lib = None
-
-
+@functools.cache
 def lib() -> C.CDLL:
-    """The product library with this layer's entries typed (the same handle as ``_capi.lib()``)."""
-    global _lib
-    if _lib is None:
-        h = picture.lib()
-        for name, (res, args) in {**SIGNATURES, **MODEL_SIGNATURES}.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = h
-    return _lib
+    """The product library with this layer's entries typed, and the picture layer's, whose histogram and tables this layer's callers
+    use beside it (the same handle as ``_capi.lib()``)."""
+    picture.lib()
+    return _capi.bind(SIGNATURES, MODEL_SIGNATURES)
 
 
 _FLOATS = ("scan_deg", "px_per_deg", "time_offset", "row_period")
@@ -268,9 +262,8 @@ def _take(res: MdemodMapResult, select) -> Map:
     """A C result into arrays of our own; the C side's memory goes back."""
     try:
         w, h, planes = int(res.width), int(res.height), int(res.planes)
-        grab = lambda p, count: np.frombuffer(C.string_at(p, count), dtype=np.uint8).copy() if count else np.zeros(0, dtype=np.uint8)
-        px = grab(res.pixels, h * w * planes).reshape((h, w, planes) if planes == 3 else (h, w))
-        return Map(px, grab(res.valid, h * w).reshape(h, w), [(int(res.lo[p]), int(res.hi[p])) for p in range(planes)], tuple(int(s) for s in select),
+        px = take_bytes(res.pixels, h * w * planes).reshape((h, w, planes) if planes == 3 else (h, w))
+        return Map(px, take_bytes(res.valid, h * w).reshape(h, w), [(int(res.lo[p]), int(res.hi[p])) for p in range(planes)], tuple(int(s) for s in select),
                    int(res.sx), float(res.sy), float(res.lat_top), float(res.lon_left), float(res.timing.row_period), int(res.timing.rows_fit),
                    int(res.timing.date), float(res.utc0))
     finally:

@@ -3,19 +3,20 @@
 Several passes, each what ``map.compose`` takes for one map, blended onto one latitude / longitude grid.  ``grid`` makes the common
 grid with every pass's nodes, ``blend`` blends device tensors through given nodes and tables on the GPU, ``compose`` chains
 everything for numpy arrays (through ``mdemod_mosaic_compose_host``, in bands) and ``images_to_mosaic`` takes a list of what
-``image.vcdu_to_image`` returns.  ``model_*`` is the host model of csrc/mosaic_host.cpp, the kernel's specification.  This module
-keeps its own binding table, as ``map.py`` does.
+``image.vcdu_to_image`` returns.  ``model_*`` is the host model of csrc/mosaic_host.cpp over csrc/warp_model.h, the kernel's
+specification.  This module keeps its own binding tables, as every layer's does; ``_capi.bind`` applies them.
 """
 from __future__ import annotations
 
 import ctypes as C
 import datetime
+import functools
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import map as _map
-from ._capi import check
+from . import _capi, map as _map
+from ._capi import check, take_bytes
 from .map import _date, _nodes_shape, _packets, world_file
 from .picture import _SLOTS, _dev_slots, _host_slots, _select, composite_select
 
@@ -76,20 +77,12 @@ MODEL_SIGNATURES = {
     "mdemod_mosaic_model_host": (C.c_int, _COMPOSE),
 }
 
-_lib = None
-
-
+@functools.cache
 def lib() -> C.CDLL:
-    """The product library with this layer's entries typed (the same handle as ``_capi.lib()``)."""
-    global _lib
-    if _lib is None:
-        h = _map.lib()
-        for name, (res, args) in {**SIGNATURES, **MODEL_SIGNATURES}.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = h
-    return _lib
+    """The product library with this layer's entries typed, and those of the map and picture layers under it (the same handle as
+    ``_capi.lib()``)."""
+    _map.lib()
+    return _capi.bind(SIGNATURES, MODEL_SIGNATURES)
 
 
 _FLOATS = ("scan_deg", "px_per_deg", "time_offset", "row_period")
@@ -277,15 +270,14 @@ def _take(res: MdemodMosaicResult, select) -> Mosaic:
     """A C result into arrays of our own; the C side's memory goes back."""
     try:
         w, h, planes, n = int(res.width), int(res.height), int(res.planes), int(res.n)
-        grab = lambda p, count: np.frombuffer(C.string_at(p, count), dtype=np.uint8).copy() if count else np.zeros(0, dtype=np.uint8)
-        px = grab(res.pixels, h * w * planes).reshape((h, w, planes) if planes == 3 else (h, w))
+        px = take_bytes(res.pixels, h * w * planes).reshape((h, w, planes) if planes == 3 else (h, w))
         records = []
         for k in range(n):
             r = _record(res.timing[k])
             r.utc0, r.covered = float(res.utc0[k]), int(res.covered[k])
             r.limits = [(int(res.lo[k][p]), int(res.hi[k][p])) for p in range(planes)]
             records.append(r)
-        return Mosaic(px, grab(res.valid, h * w).reshape(h, w), grab(res.cover, h * w).reshape(h, w), tuple(int(s) for s in select), int(res.sx), float(res.sy),
+        return Mosaic(px, take_bytes(res.valid, h * w).reshape(h, w), take_bytes(res.cover, h * w).reshape(h, w),tuple(int(s) for s in select), int(res.sx), float(res.sy),
                       float(res.lat_top), float(res.lon_left), int(res.blend), records, int(res.valid_pixels), int(res.overlap_pixels))
     finally:
         lib().mdemod_mosaic_free(C.byref(res))

@@ -9,12 +9,13 @@ csrc/picture_host.cpp, the kernels' specification.  This module keeps its own bi
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _capi
-from ._capi import check
+from ._capi import check, take_bytes
 
 SRC_WIDTH, CELLS = 1568, 14
 
@@ -51,20 +52,10 @@ MODEL_SIGNATURES = {
     "mdemod_picture_model_host": (C.c_int, [_P(MdemodPictureOpts), _P(_SLOTS), _P(_SLOTS), C.c_uint32, C.c_void_p, C.c_uint32, _P(MdemodPictureResult)]),
 }
 
-_lib = None
-
-
+@functools.cache
 def lib() -> C.CDLL:
     """The product library with this layer's entries typed (the same handle as ``_capi.lib()``)."""
-    global _lib
-    if _lib is None:
-        h = _capi.lib()
-        for name, (res, args) in {**SIGNATURES, **MODEL_SIGNATURES}.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = h
-    return _lib
+    return _capi.bind(SIGNATURES, MODEL_SIGNATURES)
 
 
 def make_opts(**opts) -> MdemodPictureOpts:
@@ -218,9 +209,8 @@ def _take(res: MdemodPictureResult, select) -> Picture:
     """A C result into arrays of our own; the C side's memory goes back."""
     try:
         w, lines, planes = int(res.width), int(res.lines), int(res.planes)
-        grab = lambda p, count: np.frombuffer(C.string_at(p, count), dtype=np.uint8).copy() if count else np.zeros(0, dtype=np.uint8)
-        px = grab(res.pixels, lines * w * planes).reshape((lines, w, planes) if planes == 3 else (lines, w))
-        return Picture(px, grab(res.valid, lines // 8 * w).reshape(lines // 8, w), [(int(res.lo[p]), int(res.hi[p])) for p in range(planes)], tuple(select))
+        px = take_bytes(res.pixels, lines * w * planes).reshape((lines, w, planes) if planes == 3 else (lines, w))
+        return Picture(px, take_bytes(res.valid, lines // 8 * w).reshape(lines // 8, w), [(int(res.lo[p]), int(res.hi[p])) for p in range(planes)], tuple(select))
     finally:
         lib().mdemod_picture_free(C.byref(res))
 

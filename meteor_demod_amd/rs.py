@@ -9,6 +9,7 @@ csrc/rs_host.cpp, the kernel's specification.  This module keeps its own binding
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from dataclasses import dataclass
 
 import numpy as np
@@ -49,20 +50,10 @@ MODEL_SIGNATURES = {
     "mdemod_rs_model_decode": (C.c_int, [_P(MdemodRsOpts), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
 }
 
-_lib = None
-
-
+@functools.cache
 def lib() -> C.CDLL:
     """The product library with this layer's entries typed (the same handle as ``_capi.lib()``)."""
-    global _lib
-    if _lib is None:
-        h = _capi.lib()
-        for name, (res, args) in {**SIGNATURES, **MODEL_SIGNATURES}.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = h
-    return _lib
+    return _capi.bind(SIGNATURES, MODEL_SIGNATURES)
 
 
 @dataclass

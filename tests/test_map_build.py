@@ -27,3 +27,5 @@ def test_map_kernels_have_no_scratch(tmp_path):
     assert len(seen) == 2 and all(v["scratch"] == 0 for v in seen.values())
     # profiles/map.md: LDS holds the tables and nothing else; registers for 8 waves per SIMD (64 VGPRs)
     assert colour["lds"] == 768 and grey["lds"] == 256 and colour["vgprs"] <= 64 and grey["vgprs"] <= 64
+    # and no more of them than before the sampling code moved to csrc/warp_device.h (profiles/map.md, "One warp sampler")
+    assert colour["vgprs"] <= 46 and grey["vgprs"] <= 28
