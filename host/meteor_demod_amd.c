@@ -61,6 +61,10 @@
  * satellite) are kept after their own maps are written, and once every file is done they are blended onto one common grid on the
  * first GPU: <base>_<tag>_mosaic.ppm / .pgm, its world file and one more line.  --mosaic-blend feather|best.  Only with --map.
  * Weak references.
+ * --overlay <file> (up to three times) and --graticule <deg|auto> go on from --map as well (include/meteor_demod_amd_overlay.h):
+ * beside every map and mosaic a second picture, <...>_map_overlay.* / <...>_mosaic_overlay.*, with the polylines of the files (a
+ * shapefile's .shp or text lines "lon lat") and the graticule drawn on it on the GPU, its own world file and one more line.  The
+ * plain pictures stay as they are.  --overlay-colour <rrggbb>, --overlay-width <pixels>.  Weak references.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -87,6 +91,7 @@
 #include "meteor_demod_amd_picture.h"
 #include "meteor_demod_amd_map.h"
 #include "meteor_demod_amd_mosaic.h"
+#include "meteor_demod_amd_overlay.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
 #endif
@@ -124,6 +129,7 @@ static const struct option longopts[] = {
 	{ "rectify", 0, NULL, 0x16 },   { "composite", 1, NULL, 0x17 }, { "altitude", 1, NULL, 0x18 }, { "scan-angle", 1, NULL, 0x19 },
 	{ "map", 1, NULL, 0x1a },       { "norad", 1, NULL, 0x1b },   { "map-scale", 1, NULL, 0x1c }, { "date", 1, NULL, 0x1d },
 	{ "time-offset", 1, NULL, 0x1e }, { "scan-side", 1, NULL, 0x1f }, { "mosaic", 1, NULL, 0x20 },   { "mosaic-blend", 1, NULL, 0x21 },
+	{ "overlay", 1, NULL, 0x22 },   { "graticule", 1, NULL, 0x23 }, { "overlay-colour", 1, NULL, 0x24 }, { "overlay-width", 1, NULL, 0x25 },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -242,6 +248,28 @@ have_mosaic(void)
 	return mdemod_mosaic_default_opts && mdemod_mosaic_compose_host && mdemod_mosaic_free;
 }
 
+/* the overlay layer's entries (include/meteor_demod_amd_overlay.h: --overlay, --graticule): weak as well */
+#pragma weak mdemod_overlay_read
+#pragma weak mdemod_overlay_graticule
+#pragma weak mdemod_overlay_vectors_free
+#pragma weak mdemod_overlay_draw_host
+
+static int
+have_overlay(void)
+{
+	return mdemod_overlay_read && mdemod_overlay_graticule && mdemod_overlay_vectors_free && mdemod_overlay_draw_host;
+}
+
+/* what --overlay / --graticule ask of every map and mosaic */
+#define OVERLAY_FILES 3
+struct overlay_req {
+	mdemod_overlay_vectors coast[OVERLAY_FILES];   /* the files of --overlay, read before anything is demodulated */
+	uint32_t n_files;
+	int      graticule;                  /* --graticule given */
+	double   step;                       /* 0: auto */
+	mdemod_overlay_style style[2];       /* 0: the files' lines, 1: the graticule */
+};
+
 /* what --vcdu / --image ask of the transfer frames of one file */
 struct vcdu_req {
 	int      write_vcdu;                 /* the .vcdu and its line */
@@ -261,6 +289,7 @@ struct vcdu_req {
 	uint32_t norad;
 	uint32_t mosaic_blend;               /* --mosaic-blend */
 	mdemod_image_result *keep;           /* --mosaic: where this file's pictures go instead of being freed (rows = 0: nothing kept) */
+	const struct overlay_req *overlay;   /* --overlay / --graticule: NULL without them */
 };
 
 /* --offset: a signed number of Hz with an optional k / M suffix (fractions kept); 1 on a malformed one */
@@ -376,7 +405,17 @@ usage(const char *prog)
 	        "                           share of valid pixels and of pixels seen by two or more passes.  The options of --map\n"
 	        "                           apply to every pass; a file without a picture is left out\n"
 	        "       --mosaic-blend <m>  With --mosaic: feather (default: the weighted mean) or best (the pass nearest its nadir)\n"
-	        "       --diff              With --cadu / --vcdu: the sender codes differentially (NRZ-M); the frame pass searches\n"
+	        "       --overlay <file>    With --map: beside every map and mosaic a second picture, <...>_map_overlay.ppm / .pgm or\n"
+        "                           <...>_mosaic_overlay.*, with the polylines of the file drawn on it on the GPU, and its own\n"
+        "                           world file; the plain pictures stay as they are.  The file is a shapefile's main file\n"
+        "                           (.shp; lines and polygons) or text, one \"lon lat\" per line, an empty line or one that\n"
+        "                           begins with > between polylines.  Up to three times.  One more line on stdout: pieces\n"
+        "                           kept, tiles touched and pixels drawn per style\n"
+        "       --graticule <deg>   With --map: meridians and parallels every <deg> degrees on the overlay picture (auto: from\n"
+        "                           the scale)\n"
+        "       --overlay-colour <rrggbb>  The colour of the lines of --overlay (default: ffff00)\n"
+        "       --overlay-width <px>       Their width in pixels (0 .. 16, default: 1)\n"
+        "       --diff              With --cadu / --vcdu: the sender codes differentially (NRZ-M); the frame pass searches\n"
 	        "                           the differential marker and undoes the coding after the Viterbi decoder\n"
 	        "       --skew              With --cadu / --vcdu: the rails may stand one symbol apart, as after -m oqpsk when\n"
 	        "                           the carrier loop settles a quarter turn off; the frame pass tries both skews as well.\n"
@@ -988,6 +1027,63 @@ map_options(const struct vcdu_req *req, mdemod_map_opts *mo)
 	if (req->side) mo->side = req->side;
 }
 
+/* --overlay / --graticule: a copy of a picture on the grid given with the lines on it: <stem>_overlay.ppm / .pgm, a world file of
+ * the picture's six lines and one line on stdout.  0, or the exit status. */
+static int
+overlay_file(const char *stem, const struct overlay_req *ov, uint32_t width, uint32_t height, uint32_t planes, uint32_t sx, double sy, double lat_top, double lon_left,
+             const uint8_t *pixels, const uint8_t *valid, int device)
+{
+	const mdemod_overlay_geo geo = { width, height, sx, 0, sy, lat_top, lon_left };
+	mdemod_overlay_vectors grat;
+	mdemod_overlay_layer layers[OVERLAY_FILES + 1];
+	mdemod_overlay_report rep;
+	uint32_t n = 0;
+	memset(&grat, 0, sizeof grat);
+	memset(layers, 0, sizeof layers);
+	if (ov->graticule) {
+		/* (the order of the layers decides no byte: style 0 meets a pixel before style 1) */
+		if (mdemod_overlay_graticule(&geo, ov->step, &grat) != MDEMOD_OK) { fprintf(stderr, "--graticule: %s\n", mdemod_last_error()); return 1; }
+		layers[n].vectors = &grat; layers[n++].style = 1;
+	}
+	for (uint32_t k = 0; k < ov->n_files; k++) { layers[n].vectors = &ov->coast[k]; layers[n++].style = 0; }
+	const size_t bytes = (size_t)height * width * planes, len = strlen(stem) + 32;
+	uint8_t *copy = malloc(bytes ? bytes : 1);
+	char *name = malloc(len);
+	int code = 0;
+	if (!copy || !name) { fprintf(stderr, "--overlay: out of memory\n"); code = 2; }
+	else {
+		memcpy(copy, pixels, bytes);
+		const int rc = mdemod_overlay_draw_host(&geo, layers, n, ov->style, 2, planes, copy, valid, NULL, 0, &rep, device);
+		if (rc != MDEMOD_OK) { fprintf(stderr, "--overlay: %s\n", why_of(rc)); code = rc == MDEMOD_ERR_PARAM ? 1 : 2; }
+	}
+	if (!code) {
+		snprintf(name, len, "%s_overlay.%s", stem, planes == 3 ? "ppm" : "pgm");
+		FILE *o = fopen(name, "wb");
+		if (!o) { fprintf(stderr, "--overlay: could not open %s\n", name); code = 1; }
+		else {
+			const int short_write = fprintf(o, "P%d\n%u %u\n255\n", planes == 3 ? 6 : 5, width, height) < 0 || fwrite(copy, 1, bytes, o) != bytes;
+			if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--overlay: writing %s failed: the picture is incomplete\n", name); code = 1; }
+		}
+	}
+	if (!code) {
+		snprintf(name, len, "%s_overlay.wld", stem);
+		FILE *o = fopen(name, "w");
+		if (!o) { fprintf(stderr, "--overlay: could not open %s\n", name); code = 1; }
+		else {
+			const int short_write = fprintf(o, "%.17g\n0\n0\n%.17g\n%.17g\n%.17g\n", 1.0 / sx, -1.0 / sy, lon_left + 0.5 / sx, lat_top - 0.5 / sy) < 0;
+			if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--overlay: writing %s failed: the world file is incomplete\n", name); code = 1; }
+		}
+	}
+	if (!code)
+		printf("%s_overlay: %llu pieces kept, %llu tiles touched; lines: %llu pieces, %llu pixels; graticule: %llu pieces, %llu pixels\n", stem,
+		       (unsigned long long)(rep.pieces[0] + rep.pieces[1]), (unsigned long long)rep.tiles, (unsigned long long)rep.pieces[0], (unsigned long long)rep.pixels[0],
+		       (unsigned long long)rep.pieces[1], (unsigned long long)rep.pixels[1]);
+	free(copy);
+	free(name);
+	mdemod_overlay_vectors_free(&grat);
+	return code;
+}
+
 /* one map of the given slots: <tag>_map.ppm / .pgm, its world file and its line.  0, or the exit status. */
 static int
 map_file(const char *s_name, const mdemod_image_result *res, const struct vcdu_req *req, const uint32_t *select, uint32_t planes, const char *tag, int device)
@@ -1029,6 +1125,13 @@ map_file(const char *s_name, const mdemod_image_result *res, const struct vcdu_r
 		       (int)(fmod(sec, 3600.0) / 60.0), fmod(sec, 60.0), 100.0 * (double)map.valid_pixels / ((double)map.width * map.height));
 	}
 	free(base);
+	if (!code && req->overlay) {
+		snprintf(ext, sizeof ext, "_%s_map", tag);
+		char *stem = beside(s_name, ext);
+		if (!stem) { fprintf(stderr, "--overlay: out of memory\n"); code = 2; }
+		else code = overlay_file(stem, req->overlay, map.width, map.height, planes, map.sx, map.sy, map.lat_top, map.lon_left, map.pixels, map.valid, device);
+		free(stem);
+	}
 	mdemod_map_free(&map);
 	return code;
 }
@@ -1110,6 +1213,16 @@ mosaic_file(const char *base, const mdemod_mosaic_pass *passes, uint32_t n, cons
 			printf("%s %04d-%02u-%02uT%02d:%02d:%06.3fZ", k ? "," : "", y, m, d, (int)(sec / 3600.0), (int)(fmod(sec, 3600.0) / 60.0), fmod(sec, 60.0));
 		}
 		printf("; %.1f %% of pixels valid; %.1f %% seen by two or more passes\n", 100.0 * (double)mos.valid_pixels / area, 100.0 * (double)mos.overlap_pixels / area);
+	}
+	if (!code && req->overlay) {
+		const size_t stem_len = strlen(base) + strlen(tag) + 16;
+		char *stem = malloc(stem_len);
+		if (!stem) { fprintf(stderr, "--overlay: out of memory\n"); code = 2; }
+		else {
+			snprintf(stem, stem_len, "%s_%s_mosaic", base, tag);
+			code = overlay_file(stem, req->overlay, mos.width, mos.height, planes, mos.sx, mos.sy, mos.lat_top, mos.lon_left, mos.pixels, mos.valid, device);
+		}
+		free(stem);
 	}
 	mdemod_mosaic_free(&mos);
 	return code;
@@ -1338,6 +1451,10 @@ main(int argc, char **argv)
 	uint32_t map_norad = 0;
 	int mosaic_blend_given = 0;
 	struct vcdu_req vreq = { 0, 0, { 64, 65, 66 }, 0, 0, { 2, 1, 0 }, 0.0, 0.0 };
+	/* --overlay: yellow, one pixel, opaque; --graticule: grey, one pixel, opacity 160 */
+	static struct overlay_req oreq = { .style = { { 128, 256, { 255, 255, 0 }, 0 }, { 128, 160, { 128, 128, 128 }, 0 } } };
+	const char *overlay_fname[OVERLAY_FILES] = { NULL, NULL, NULL };
+	int n_overlay = 0, overlay_opts_given = 0;
 	long int_delay = MDEMOD_IL_DEFAULT_BRANCH_DELAY;
 	double *auto_offsets = NULL;               /* --offset auto: the offset chosen for each file */
 #ifdef MDEMOD_TUI
@@ -1439,6 +1556,37 @@ main(int argc, char **argv)
 			map_opts_given = 1;
 			break;
 		case 0x20: mosaic_base = optarg; break;
+		case 0x22:
+			if (n_overlay == OVERLAY_FILES) { fprintf(stderr, "--overlay: at most %d files\n", OVERLAY_FILES); return 1; }
+			overlay_fname[n_overlay++] = optarg;
+			break;
+		case 0x23: {
+			char *end = optarg;
+			const int automatic = !strcmp(optarg, "auto");
+			oreq.graticule = 1;
+			oreq.step = automatic ? 0.0 : strtod(optarg, &end);
+			if (!automatic && (end == optarg || *end || !(oreq.step >= 0.01 && oreq.step <= 90.0))) {
+				fprintf(stderr, "--graticule: a number of degrees (0.01 .. 90) or auto\n");
+				return 1;
+			}
+			break;
+		}
+		case 0x24: {
+			unsigned r, g, b;
+			char tail;
+			if (strlen(optarg) != 6 || sscanf(optarg, "%2x%2x%2x%c", &r, &g, &b, &tail) != 3) { fprintf(stderr, "--overlay-colour: six hexadecimal digits, rrggbb\n"); return 1; }
+			oreq.style[0].colour[0] = (uint8_t)r; oreq.style[0].colour[1] = (uint8_t)g; oreq.style[0].colour[2] = (uint8_t)b;
+			overlay_opts_given = 1;
+			break;
+		}
+		case 0x25: {
+			char *end;
+			const double w = strtod(optarg, &end);
+			if (end == optarg || *end || !(w >= 0.0 && w <= 16.0)) { fprintf(stderr, "--overlay-width: a number of pixels, 0 .. 16\n"); return 1; }
+			oreq.style[0].half_width = (uint32_t)(128.0 * w + 0.5);
+			overlay_opts_given = 1;
+			break;
+		}
 		case 0x21:
 			if (!strcmp(optarg, "feather")) vreq.mosaic_blend = MDEMOD_MOSAIC_FEATHER;
 			else if (!strcmp(optarg, "best")) vreq.mosaic_blend = MDEMOD_MOSAIC_BEST;
@@ -1532,6 +1680,10 @@ main(int argc, char **argv)
 		fprintf(stderr, "--mosaic: this library has no mosaic layer (built without include/meteor_demod_amd_mosaic.h's entries)\n");
 		return 1;
 	}
+	if ((n_overlay || oreq.graticule || overlay_opts_given) && !have_overlay()) {
+		fprintf(stderr, "--overlay / --graticule: this library has no overlay layer (built without include/meteor_demod_amd_overlay.h's entries)\n");
+		return 1;
+	}
 	if (map_fname && !(have_map() && have_picture())) {
 		fprintf(stderr, "--map: this library has no map layer (built without include/meteor_demod_amd_map.h's entries)\n");
 		return 1;
@@ -1570,6 +1722,14 @@ main(int argc, char **argv)
 		fprintf(stderr, "--mosaic-blend: only with --mosaic (it is its option)\n");
 		return 1;
 	}
+	if ((n_overlay || oreq.graticule) && !(map_fname && want_image)) {
+		fprintf(stderr, "--overlay / --graticule: only with --map (they draw on its pictures)\n");
+		return 1;
+	}
+	if (overlay_opts_given && !n_overlay) {
+		fprintf(stderr, "--overlay-colour / --overlay-width: only with --overlay (they are its options)\n");
+		return 1;
+	}
 	if (mosaic_base && n_files > MDEMOD_MOSAIC_MAX_PASSES) {
 		fprintf(stderr, "--mosaic: %d input files are more than a mosaic takes (1 .. 8 passes)\n", n_files);
 		return 1;
@@ -1596,6 +1756,12 @@ main(int argc, char **argv)
 		vreq.tle_text = text;
 		vreq.norad = map_norad;
 	}
+	/* the vector files are read, and refused, before anything is demodulated */
+	for (int k = 0; k < n_overlay; k++) {
+		if (mdemod_overlay_read(overlay_fname[k], &oreq.coast[k]) != MDEMOD_OK) { fprintf(stderr, "--overlay: %s: %s\n", overlay_fname[k], mdemod_last_error()); return 1; }
+		oreq.n_files++;
+	}
+	if (n_overlay || oreq.graticule) vreq.overlay = &oreq;
 	if (geometry_given && !vreq.rectify && (altitude_given || !map_fname)) {
 		fprintf(stderr, "--altitude / --scan-angle: only with --rectify (they are the geometry it takes out)\n");
 		return 1;
