@@ -65,6 +65,8 @@
  * beside every map and mosaic a second picture, <...>_map_overlay.* / <...>_mosaic_overlay.*, with the polylines of the files (a
  * shapefile's .shp or text lines "lon lat") and the graticule drawn on it on the GPU, its own world file and one more line.  The
  * plain pictures stay as they are.  --overlay-colour <rrggbb>, --overlay-width <pixels>.  Weak references.
+ * --jpeg <quality> changes the format of every picture above (include/meteor_demod_amd_jpeg.h): a baseline JPEG encoded on the GPU,
+ * <same name>.jpg instead of .pgm / .ppm, one line per file and one at the end.  Only with --image.  Weak references.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -92,6 +94,7 @@
 #include "meteor_demod_amd_map.h"
 #include "meteor_demod_amd_mosaic.h"
 #include "meteor_demod_amd_overlay.h"
+#include "meteor_demod_amd_jpeg.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
 #endif
@@ -130,6 +133,7 @@ static const struct option longopts[] = {
 	{ "map", 1, NULL, 0x1a },       { "norad", 1, NULL, 0x1b },   { "map-scale", 1, NULL, 0x1c }, { "date", 1, NULL, 0x1d },
 	{ "time-offset", 1, NULL, 0x1e }, { "scan-side", 1, NULL, 0x1f }, { "mosaic", 1, NULL, 0x20 },   { "mosaic-blend", 1, NULL, 0x21 },
 	{ "overlay", 1, NULL, 0x22 },   { "graticule", 1, NULL, 0x23 }, { "overlay-colour", 1, NULL, 0x24 }, { "overlay-width", 1, NULL, 0x25 },
+	{ "jpeg", 1, NULL, 0x26 },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -258,6 +262,16 @@ static int
 have_overlay(void)
 {
 	return mdemod_overlay_read && mdemod_overlay_graticule && mdemod_overlay_vectors_free && mdemod_overlay_draw_host;
+}
+
+/* the JPEG encoder's entries (include/meteor_demod_amd_jpeg.h: --jpeg): weak as well */
+#pragma weak mdemod_jpeg_encode_host
+#pragma weak mdemod_jpeg_free
+
+static int
+have_jpeg(void)
+{
+	return mdemod_jpeg_encode_host && mdemod_jpeg_free;
 }
 
 /* what --overlay / --graticule ask of every map and mosaic */
@@ -415,6 +429,10 @@ usage(const char *prog)
         "                           the scale)\n"
         "       --overlay-colour <rrggbb>  The colour of the lines of --overlay (default: ffff00)\n"
         "       --overlay-width <px>       Their width in pixels (0 .. 16, default: 1)\n"
+        "       --jpeg <quality>    With --image: every picture (the channels, _rect, the composite, _map, _mosaic, _overlay) as a\n"
+        "                           baseline JPEG <same name>.jpg of that quality (1 .. 100), encoded on the GPU, instead of the\n"
+        "                           .pgm / .ppm; world files keep their names.  One line on stdout per file, and one at the end:\n"
+        "                           files, bytes of pictures in, bytes of JPEG out\n"
         "       --diff              With --cadu / --vcdu: the sender codes differentially (NRZ-M); the frame pass searches\n"
 	        "                           the differential marker and undoes the coding after the Viterbi decoder\n"
 	        "       --skew              With --cadu / --vcdu: the rails may stand one symbol apart, as after -m oqpsk when\n"
@@ -924,6 +942,39 @@ beside(const char *s_name, const char *ext)
 	return out;
 }
 
+/* --jpeg: the quality (0: not given) and what went through the encoder.  The pictures are written by one thread, after the workers
+ * have joined. */
+static struct { unsigned quality; unsigned long long files, bytes_in, bytes_out; } jpeg_req;
+
+/* One picture of the program, pixels[height][width][planes], into `name`, which ends in ".pgm" or ".ppm": as that binary P5 / P6
+ * file, or with --jpeg encoded on the GPU into the same name ending in ".jpg" (`name` is changed), with one line on stdout that names
+ * the file.  `what` is the option the messages begin with.  0, or the exit status. */
+static int
+write_picture(const char *what, char *name, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t planes, int device)
+{
+	const size_t bytes = (size_t)height * width * planes;
+	uint8_t *file = NULL;
+	uint64_t file_bytes = 0;
+	if (jpeg_req.quality) {
+		const int rc = mdemod_jpeg_encode_host(pixels, width, height, planes, jpeg_req.quality, 0, &file, &file_bytes, device);
+		if (rc != MDEMOD_OK) { fprintf(stderr, "--jpeg: %s: %s\n", name, why_of(rc)); return rc == MDEMOD_ERR_PARAM ? 1 : 2; }
+		memcpy(name + strlen(name) - 3, "jpg", 3);
+	}
+	FILE *o = fopen(name, "wb");
+	if (!o) { fprintf(stderr, "%s: could not open %s\n", what, name); if (file) mdemod_jpeg_free(file); return 1; }
+	int short_write;
+	if (jpeg_req.quality) short_write = fwrite(file, 1, file_bytes, o) != file_bytes;
+	else short_write = fprintf(o, "P%d\n%u %u\n255\n", planes == 3 ? 6 : 5, width, height) < 0 || (bytes && fwrite(pixels, 1, bytes, o) != bytes);
+	if (jpeg_req.quality) mdemod_jpeg_free(file);
+	if ((fclose(o) != 0) | short_write) { fprintf(stderr, "%s: writing %s failed: the picture is incomplete\n", what, name); return 1; }
+	if (jpeg_req.quality) {
+		printf("%s: JPEG quality %u: %u x %u x %u, %llu bytes of %llu\n", name, jpeg_req.quality, width, height, planes, (unsigned long long)file_bytes,
+		       (unsigned long long)bytes);
+		jpeg_req.files++; jpeg_req.bytes_in += bytes; jpeg_req.bytes_out += file_bytes;
+	}
+	return 0;
+}
+
 /* --rectify / --composite: the pictures of one file through the picture layer.  One <apid>_rect.pgm per channel that received a
  * strip (--rectify), one <abc>.ppm and its line (--composite).  0, or the exit status. */
 static int
@@ -948,13 +999,8 @@ picture_files(const char *s_name, const mdemod_image_result *res, const struct v
 		char ext[32];
 		snprintf(ext, sizeof ext, "_%u_rect.pgm", (unsigned)req->apids[k]);
 		char *name = beside(s_name, ext);
-		FILE *o = name ? fopen(name, "wb") : NULL;
-		if (!o) { fprintf(stderr, "--rectify: could not open %s\n", name ? name : "the picture"); code = 1; }
-		else {
-			const size_t bytes = (size_t)pic.lines * pic.width;
-			const int short_write = fprintf(o, "P5\n%u %u\n255\n", pic.width, pic.lines) < 0 || fwrite(pic.pixels, 1, bytes, o) != bytes;
-			if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--rectify: writing %s failed: the picture is incomplete\n", name); code = 1; }
-		}
+		if (!name) { fprintf(stderr, "--rectify: could not open the picture\n"); code = 1; }
+		else code = write_picture("--rectify", name, pic.pixels, pic.width, pic.lines, 1, device);
 		free(name);
 		mdemod_picture_free(&pic);
 	}
@@ -976,13 +1022,8 @@ picture_files(const char *s_name, const mdemod_image_result *res, const struct v
 	char ext[32];
 	snprintf(ext, sizeof ext, "_%u%u%u.ppm", (unsigned)select[0] + 1, (unsigned)select[1] + 1, (unsigned)select[2] + 1);
 	char *name = beside(s_name, ext);
-	FILE *o = name ? fopen(name, "wb") : NULL;
-	if (!o) { fprintf(stderr, "--composite: could not open %s\n", name ? name : "the picture"); code = 1; }
-	else {
-		const size_t bytes = (size_t)pic.lines * pic.width * 3;
-		const int short_write = fprintf(o, "P6\n%u %u\n255\n", pic.width, pic.lines) < 0 || (bytes && fwrite(pic.pixels, 1, bytes, o) != bytes);
-		if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--composite: writing %s failed: the picture is incomplete\n", name); code = 1; }
-	}
+	if (!name) { fprintf(stderr, "--composite: could not open the picture\n"); code = 1; }
+	else code = write_picture("--composite", name, pic.pixels, pic.width, pic.lines, 3, device);
 	if (!code)
 		printf("%s: composite %u%u%u: %u x %u%s; stretch R %u .. %u, G %u .. %u, B %u .. %u; %.1f %% of pixels valid\n", base ? base : s_name,
 		       (unsigned)select[0] + 1, (unsigned)select[1] + 1, (unsigned)select[2] + 1, pic.width, pic.lines, req->rectify ? " rectified" : "",
@@ -1058,12 +1099,7 @@ overlay_file(const char *stem, const struct overlay_req *ov, uint32_t width, uin
 	}
 	if (!code) {
 		snprintf(name, len, "%s_overlay.%s", stem, planes == 3 ? "ppm" : "pgm");
-		FILE *o = fopen(name, "wb");
-		if (!o) { fprintf(stderr, "--overlay: could not open %s\n", name); code = 1; }
-		else {
-			const int short_write = fprintf(o, "P%d\n%u %u\n255\n", planes == 3 ? 6 : 5, width, height) < 0 || fwrite(copy, 1, bytes, o) != bytes;
-			if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--overlay: writing %s failed: the picture is incomplete\n", name); code = 1; }
-		}
+		code = write_picture("--overlay", name, copy, width, height, planes, device);
 	}
 	if (!code) {
 		snprintf(name, len, "%s_overlay.wld", stem);
@@ -1098,17 +1134,12 @@ map_file(const char *s_name, const mdemod_image_result *res, const struct vcdu_r
 	char ext[48];
 	snprintf(ext, sizeof ext, "_%s_map.%s", tag, planes == 3 ? "ppm" : "pgm");
 	char *name = beside(s_name, ext), *base = beside(s_name, "");
-	FILE *o = name ? fopen(name, "wb") : NULL;
-	if (!o) { fprintf(stderr, "--map: could not open %s\n", name ? name : "the picture"); code = 1; }
-	else {
-		const size_t bytes = (size_t)map.height * map.width * planes;
-		const int short_write = fprintf(o, "P%d\n%u %u\n255\n", planes == 3 ? 6 : 5, map.width, map.height) < 0 || fwrite(map.pixels, 1, bytes, o) != bytes;
-		if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--map: writing %s failed: the picture is incomplete\n", name); code = 1; }
-	}
+	if (!name) { fprintf(stderr, "--map: could not open the picture\n"); code = 1; }
+	else code = write_picture("--map", name, map.pixels, map.width, map.height, planes, device);
 	free(name);
 	snprintf(ext, sizeof ext, "_%s_map.wld", tag);
 	name = code ? NULL : beside(s_name, ext);
-	o = name ? fopen(name, "w") : NULL;
+	FILE *o = name ? fopen(name, "w") : NULL;
 	if (!code && !o) { fprintf(stderr, "--map: could not open %s\n", name ? name : "the world file"); code = 1; }
 	else if (!code) {
 		const int short_write = fprintf(o, "%.17g\n0\n0\n%.17g\n%.17g\n%.17g\n", 1.0 / map.sx, -1.0 / map.sy, map.lon_left + 0.5 / map.sx, map.lat_top - 0.5 / map.sy) < 0;
@@ -1184,16 +1215,11 @@ mosaic_file(const char *base, const mdemod_mosaic_pass *passes, uint32_t n, cons
 	const size_t len = strlen(base) + strlen(tag) + 32;
 	char *name = malloc(len);
 	if (name) snprintf(name, len, "%s_%s_mosaic.%s", base, tag, planes == 3 ? "ppm" : "pgm");
-	FILE *o = name ? fopen(name, "wb") : NULL;
-	if (!o) { fprintf(stderr, "--mosaic: could not open %s\n", name ? name : "the picture"); code = 1; }
-	else {
-		const size_t bytes = (size_t)mos.height * mos.width * planes;
-		const int short_write = fprintf(o, "P%d\n%u %u\n255\n", planes == 3 ? 6 : 5, mos.width, mos.height) < 0 || fwrite(mos.pixels, 1, bytes, o) != bytes;
-		if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--mosaic: writing %s failed: the picture is incomplete\n", name); code = 1; }
-	}
+	if (!name) { fprintf(stderr, "--mosaic: could not open the picture\n"); code = 1; }
+	else code = write_picture("--mosaic", name, mos.pixels, mos.width, mos.height, planes, device);
 	if (!code) {
 		snprintf(name, len, "%s_%s_mosaic.wld", base, tag);
-		o = fopen(name, "w");
+		FILE *o = fopen(name, "w");
 		if (!o) { fprintf(stderr, "--mosaic: could not open %s\n", name); code = 1; }
 		else {
 			const int short_write = fprintf(o, "%.17g\n0\n0\n%.17g\n%.17g\n%.17g\n", 1.0 / mos.sx, -1.0 / mos.sy, mos.lon_left + 0.5 / mos.sx, mos.lat_top - 0.5 / mos.sy) < 0;
@@ -1299,11 +1325,8 @@ image_files(const char *s_name, const uint8_t *vcdu, const mdemod_rs_info *info,
 		char ext[32];
 		snprintf(ext, sizeof ext, "_%u.pgm", (unsigned)apids[k]);
 		char *name = beside(s_name, ext);
-		FILE *o = name ? fopen(name, "wb") : NULL;
-		if (!o) { fprintf(stderr, "--image: could not open %s\n", name ? name : "the picture"); free(name); code = 1; break; }
-		const size_t bytes = (size_t)rows * 8 * MDEMOD_IMAGE_WIDTH;
-		const int short_write = fprintf(o, "P5\n%d %u\n255\n", MDEMOD_IMAGE_WIDTH, rows * 8) < 0 || fwrite(res.image[k], 1, bytes, o) != bytes;
-		if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--image: writing %s failed: the picture is incomplete\n", name); code = 1; }
+		if (!name) { fprintf(stderr, "--image: could not open the picture\n"); code = 1; break; }
+		code = write_picture("--image", name, res.image[k], MDEMOD_IMAGE_WIDTH, rows * 8, 1, device);
 		free(name);
 	}
 	if (!code) {
@@ -1587,6 +1610,13 @@ main(int argc, char **argv)
 			overlay_opts_given = 1;
 			break;
 		}
+		case 0x26: {
+			char *end;
+			const long q = strtol(optarg, &end, 10);
+			if (end == optarg || *end || q < 1 || q > 100) { fprintf(stderr, "--jpeg: a quality, 1 .. 100\n"); return 1; }
+			jpeg_req.quality = (unsigned)q;
+			break;
+		}
 		case 0x21:
 			if (!strcmp(optarg, "feather")) vreq.mosaic_blend = MDEMOD_MOSAIC_FEATHER;
 			else if (!strcmp(optarg, "best")) vreq.mosaic_blend = MDEMOD_MOSAIC_BEST;
@@ -1728,6 +1758,14 @@ main(int argc, char **argv)
 	}
 	if (overlay_opts_given && !n_overlay) {
 		fprintf(stderr, "--overlay-colour / --overlay-width: only with --overlay (they are its options)\n");
+		return 1;
+	}
+	if (jpeg_req.quality && !want_image) {
+		fprintf(stderr, "--jpeg: only with --image (it is the format of its pictures)\n");
+		return 1;
+	}
+	if (jpeg_req.quality && !have_jpeg()) {
+		fprintf(stderr, "--jpeg: this build of libmeteor_demod_amd has no JPEG encoder\n");
 		return 1;
 	}
 	if (mosaic_base && n_files > MDEMOD_MOSAIC_MAX_PASSES) {
@@ -2023,5 +2061,7 @@ main(int argc, char **argv)
 		if (rc_all == 0) rc_all = mosaic_files(mosaic_base, kept, io, n_files, &vreq, devs[0]);
 		else for (int i = 0; i < n_files; i++) mdemod_image_free(&kept[i]);
 	}
+	if (jpeg_req.quality && rc_all == 0)
+		printf("--jpeg %u: %llu files, %llu bytes of pictures in, %llu bytes of JPEG out\n", jpeg_req.quality, jpeg_req.files, jpeg_req.bytes_in, jpeg_req.bytes_out);
 	LEAVE(rc_all);
 }
