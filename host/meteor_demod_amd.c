@@ -65,6 +65,9 @@
  * beside every map and mosaic a second picture, <...>_map_overlay.* / <...>_mosaic_overlay.*, with the polylines of the files (a
  * shapefile's .shp or text lines "lon lat") and the graticule drawn on it on the GPU, its own world file and one more line.  The
  * plain pictures stay as they are.  --overlay-colour <rrggbb>, --overlay-width <pixels>.  Weak references.
+ * --map-proj stereo puts the pictures of --map (and of --mosaic, --overlay, --graticule) on a polar stereographic grid instead
+ * (include/meteor_demod_amd_polar.h), for passes over a pole: <...>_polar.* with a world file and a .prj, <...>_polar_overlay.*;
+ * --map-res <metres>, --map-lon0 <deg|auto>, --map-lat-ts <deg>.  Without it nothing changes.  Weak references.
  * --jpeg <quality> changes the format of every picture above (include/meteor_demod_amd_jpeg.h): a baseline JPEG encoded on the GPU,
  * <same name>.jpg instead of .pgm / .ppm, one line per file and one at the end.  Only with --image.  Weak references.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
@@ -93,6 +96,7 @@
 #include "meteor_demod_amd_picture.h"
 #include "meteor_demod_amd_map.h"
 #include "meteor_demod_amd_mosaic.h"
+#include "meteor_demod_amd_polar.h"
 #include "meteor_demod_amd_overlay.h"
 #include "meteor_demod_amd_jpeg.h"
 #ifdef MDEMOD_TUI
@@ -133,7 +137,8 @@ static const struct option longopts[] = {
 	{ "map", 1, NULL, 0x1a },       { "norad", 1, NULL, 0x1b },   { "map-scale", 1, NULL, 0x1c }, { "date", 1, NULL, 0x1d },
 	{ "time-offset", 1, NULL, 0x1e }, { "scan-side", 1, NULL, 0x1f }, { "mosaic", 1, NULL, 0x20 },   { "mosaic-blend", 1, NULL, 0x21 },
 	{ "overlay", 1, NULL, 0x22 },   { "graticule", 1, NULL, 0x23 }, { "overlay-colour", 1, NULL, 0x24 }, { "overlay-width", 1, NULL, 0x25 },
-	{ "jpeg", 1, NULL, 0x26 },
+	{ "jpeg", 1, NULL, 0x26 },      { "map-proj", 1, NULL, 0x27 },  { "map-res", 1, NULL, 0x28 },   { "map-lon0", 1, NULL, 0x29 },
+	{ "map-lat-ts", 1, NULL, 0x2a },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -252,6 +257,24 @@ have_mosaic(void)
 	return mdemod_mosaic_default_opts && mdemod_mosaic_compose_host && mdemod_mosaic_free;
 }
 
+/* the polar layer's entries (include/meteor_demod_amd_polar.h: --map-proj stereo): weak as well */
+#pragma weak mdemod_polar_default_opts
+#pragma weak mdemod_polar_compose_host
+#pragma weak mdemod_polar_free
+#pragma weak mdemod_polar_graticule
+#pragma weak mdemod_polar_lines_free
+#pragma weak mdemod_polar_vertices
+#pragma weak mdemod_polar_points_free
+#pragma weak mdemod_polar_draw_host
+#pragma weak mdemod_polar_world_file
+#pragma weak mdemod_polar_prj
+static int
+have_polar(void)
+{
+	return mdemod_polar_default_opts && mdemod_polar_compose_host && mdemod_polar_free && mdemod_polar_graticule && mdemod_polar_lines_free && mdemod_polar_vertices &&
+	       mdemod_polar_points_free && mdemod_polar_draw_host && mdemod_polar_world_file && mdemod_polar_prj;
+}
+
 /* the overlay layer's entries (include/meteor_demod_amd_overlay.h: --overlay, --graticule): weak as well */
 #pragma weak mdemod_overlay_read
 #pragma weak mdemod_overlay_graticule
@@ -304,6 +327,10 @@ struct vcdu_req {
 	uint32_t mosaic_blend;               /* --mosaic-blend */
 	mdemod_image_result *keep;           /* --mosaic: where this file's pictures go instead of being freed (rows = 0: nothing kept) */
 	const struct overlay_req *overlay;   /* --overlay / --graticule: NULL without them */
+	int      polar;                      /* --map-proj stereo: _polar.* on a polar stereographic grid instead of _map.* / _mosaic.* */
+	double   polar_res, polar_lat_ts;    /* --map-res, --map-lat-ts (0: the defaults) */
+	double   polar_lon0;                 /* --map-lon0 when lon0_given (otherwise the pass's own) */
+	int      lon0_given;
 };
 
 /* --offset: a signed number of Hz with an optional k / M suffix (fractions kept); 1 on a malformed one */
@@ -410,6 +437,15 @@ usage(const char *prog)
 	        "       --date <yyyy-mm-dd> With --map: the date of the first line's onboard time (default: the one nearest the epoch)\n"
 	        "       --time-offset <s>   With --map: onboard clock minus UTC in seconds (default: 10800, Moscow time)\n"
 	        "       --scan-side <1|-1>  With --map: which way the mirror turns (default: 1)\n"
+	        "       --map-proj <p>      With --map: latlon (default) or stereo: a polar stereographic grid on WGS-84 in metres, for\n"
+	        "                           passes over a pole, which the latitude / longitude grid refuses beyond 85 degrees.  The\n"
+	        "                           pictures are <output>_<tag>_polar.ppm / .pgm instead of _map.*, each with a world file\n"
+	        "                           (.wld) and the projection as WKT (.prj); with --mosaic also <base>_<tag>_polar.* of all\n"
+	        "                           passes; --overlay and --graticule draw onto _polar_overlay.*; one line on stdout each\n"
+	        "       --map-res <metres>  With --map-proj stereo: metres per pixel (100 .. 100000, default: 1000)\n"
+	        "       --map-lon0 <deg|auto>  With --map-proj stereo: the meridian that points down (north) or up (south) in the\n"
+	        "                           picture (default: auto, the longitude of the pass's middle rounded to a degree)\n"
+	        "       --map-lat-ts <deg>  With --map-proj stereo: the latitude of true scale, a magnitude (default: 70)\n"
 	        "       --mosaic <base>     With --map: the input files (1 .. 8) are passes of one satellite; besides each file's own\n"
 	        "                           maps all passes are blended onto one common grid on the first GPU, where several saw the\n"
 	        "                           same ground weighted by the distance from the edge of the swath: <base>_<abc>_mosaic.ppm\n"
@@ -1304,6 +1340,171 @@ mosaic_files(const char *base, mdemod_image_result *kept, const struct stream_io
 	return code;
 }
 
+/* --map-proj stereo with --overlay / --graticule: a copy of a polar picture with the lines on it, <stem>_overlay.ppm / .pgm with the
+ * picture's world file and .prj, and one line.  The lines go through the polar layer's vertices and the overlay layer's kernel. */
+static int
+polar_overlay_file(const char *stem, const struct overlay_req *ov, const mdemod_polar_result *pic, const char *wld, const char *prj, int device)
+{
+	const mdemod_polar_frame *f = &pic->frame;
+	mdemod_polar_lines grat;
+	mdemod_polar_points pts[OVERLAY_FILES + 1];
+	const mdemod_polar_points *layers[OVERLAY_FILES + 1];
+	uint32_t style_of[OVERLAY_FILES + 1], n = 0;
+	mdemod_polar_style styles[2];
+	mdemod_polar_drawn rep;
+	int code = 0;
+	memset(&grat, 0, sizeof grat);
+	memset(pts, 0, sizeof pts);
+	memset(&rep, 0, sizeof rep);
+	for (int s = 0; s < 2; s++) {
+		styles[s].half_width = ov->style[s].half_width; styles[s].opacity = ov->style[s].opacity; styles[s].inside_only = ov->style[s].inside_only;
+		memcpy(styles[s].colour, ov->style[s].colour, 3);
+	}
+	if (ov->graticule) {
+		if (mdemod_polar_graticule(f, ov->step, &grat) != MDEMOD_OK || mdemod_polar_vertices(f, grat.lon, grat.lat, grat.first, grat.n_lines, &pts[n]) != MDEMOD_OK) {
+			fprintf(stderr, "--graticule: %s\n", mdemod_last_error());
+			code = 1;
+		} else { layers[n] = &pts[n]; style_of[n++] = 1; }
+	}
+	for (uint32_t k = 0; k < ov->n_files && !code; k++) {
+		if (mdemod_polar_vertices(f, ov->coast[k].lon, ov->coast[k].lat, ov->coast[k].first, ov->coast[k].n_lines, &pts[n]) != MDEMOD_OK) {
+			fprintf(stderr, "--overlay: %s\n", mdemod_last_error());
+			code = 1;
+		} else { layers[n] = &pts[n]; style_of[n++] = 0; }
+	}
+	const size_t bytes = (size_t)f->height * f->width * pic->planes, len = strlen(stem) + 32;
+	uint8_t *copy = malloc(bytes ? bytes : 1);
+	char *name = malloc(len);
+	if (!code && (!copy || !name)) { fprintf(stderr, "--overlay: out of memory\n"); code = 2; }
+	if (!code) {
+		memcpy(copy, pic->pixels, bytes);
+		const int rc = mdemod_polar_draw_host(layers, style_of, n, styles, 2, f->width, f->height, pic->planes, copy, pic->valid, &rep, device);
+		if (rc != MDEMOD_OK) { fprintf(stderr, "--overlay: %s\n", why_of(rc)); code = rc == MDEMOD_ERR_PARAM ? 1 : 2; }
+	}
+	if (!code) {
+		snprintf(name, len, "%s_overlay.%s", stem, pic->planes == 3 ? "ppm" : "pgm");
+		code = write_picture("--overlay", name, copy, f->width, f->height, pic->planes, device);
+	}
+	for (int t = 0; t < 2 && !code; t++) {
+		snprintf(name, len, "%s_overlay.%s", stem, t ? "prj" : "wld");
+		FILE *o = fopen(name, "w");
+		if (!o) { fprintf(stderr, "--overlay: could not open %s\n", name); code = 1; }
+		else if ((fputs(t ? prj : wld, o) < 0) | (fclose(o) != 0)) { fprintf(stderr, "--overlay: writing %s failed\n", name); code = 1; }
+	}
+	if (!code)
+		printf("%s_overlay: %llu pieces kept, %llu tiles touched; lines: %llu pieces; graticule: %llu pieces every %g degrees\n", stem,
+		       (unsigned long long)(rep.pieces[0] + rep.pieces[1]), (unsigned long long)rep.tiles, (unsigned long long)rep.pieces[0], (unsigned long long)rep.pieces[1],
+		       grat.step_deg);
+	free(copy);
+	free(name);
+	for (uint32_t k = 0; k < OVERLAY_FILES + 1; k++) mdemod_polar_points_free(&pts[k]);
+	mdemod_polar_lines_free(&grat);
+	return code;
+}
+
+/* --map-proj stereo: one picture of the given slots of n passes: <stem>_<tag>_polar.ppm / .pgm, its world file, its .prj and its
+ * line.  0, or the exit status. */
+static int
+polar_file(const char *stem, const mdemod_polar_pass *passes, uint32_t n, const struct vcdu_req *req, const uint32_t *select, uint32_t planes, const char *tag, int device)
+{
+	mdemod_polar_opts po;
+	mdemod_polar_result pic;
+	mdemod_polar_default_opts(&po);
+	if (req->scan_deg != 0.0) po.scan_deg = req->scan_deg;
+	if (req->offset_given) po.time_offset = req->time_offset;
+	if (req->side) po.side = req->side;
+	if (req->polar_res != 0.0) po.metres_per_pixel = req->polar_res;
+	if (req->polar_lat_ts != 0.0) po.lat_ts_deg = req->polar_lat_ts;
+	if (req->lon0_given) po.lon0_deg = req->polar_lon0;
+	po.blend = req->mosaic_blend;
+	const int rc = mdemod_polar_compose_host(&po, passes, n, select, planes, &pic, device);
+	if (rc != MDEMOD_OK) { fprintf(stderr, "--map-proj stereo: %s: %s\n", stem, why_of(rc)); return rc == MDEMOD_ERR_PARAM ? 1 : 2; }
+	int code = 0;
+	char wld[256], prj[1024];
+	if (mdemod_polar_world_file(&pic.frame, wld, sizeof wld) != MDEMOD_OK || mdemod_polar_prj(&pic.frame, prj, sizeof prj) != MDEMOD_OK) {
+		fprintf(stderr, "--map-proj stereo: %s\n", mdemod_last_error());
+		code = 2;
+	}
+	const size_t len = strlen(stem) + strlen(tag) + 32;
+	char *name = malloc(len);
+	if (!code && !name) { fprintf(stderr, "--map-proj stereo: out of memory\n"); code = 2; }
+	if (!code) {
+		snprintf(name, len, "%s_%s_polar.%s", stem, tag, planes == 3 ? "ppm" : "pgm");
+		code = write_picture("--map-proj stereo", name, pic.pixels, pic.frame.width, pic.frame.height, planes, device);
+	}
+	for (int t = 0; t < 2 && !code; t++) {
+		snprintf(name, len, "%s_%s_polar.%s", stem, tag, t ? "prj" : "wld");
+		FILE *o = fopen(name, "w");
+		if (!o) { fprintf(stderr, "--map-proj stereo: could not open %s\n", name); code = 1; }
+		else if ((fputs(t ? prj : wld, o) < 0) | (fclose(o) != 0)) { fprintf(stderr, "--map-proj stereo: writing %s failed\n", name); code = 1; }
+	}
+	if (!code) {
+		const double area = (double)pic.frame.width * pic.frame.height;
+		printf("%s: polar %s (%s): %u x %u at %g m; %s pole, central meridian %g, true scale at %g; E %.0f .. %.0f, N %.0f .. %.0f; %u pass%s; first lines", stem, tag,
+		       pic.blend == MDEMOD_POLAR_BEST ? "best" : "feather", pic.frame.width, pic.frame.height, pic.frame.res, pic.frame.pole > 0 ? "north" : "south",
+		       pic.frame.lon0_deg, pic.frame.lat_ts_deg, pic.frame.e_left, pic.frame.e_left + pic.frame.width * pic.frame.res,
+		       pic.frame.n_top - pic.frame.height * pic.frame.res, pic.frame.n_top, pic.n, pic.n == 1 ? "" : "es");
+		for (uint32_t k = 0; k < pic.n; k++) {
+			const double total = (double)pic.timing[k].date * 86400.0 + pic.utc0[k], day = floor(total / 86400.0), sec = total - day * 86400.0;
+			int y; unsigned m, d;
+			civil_from_days((int64_t)day, &y, &m, &d);
+			printf("%s %04d-%02u-%02uT%02d:%02d:%06.3fZ", k ? "," : "", y, m, d, (int)(sec / 3600.0), (int)(fmod(sec, 3600.0) / 60.0), fmod(sec, 60.0));
+		}
+		printf("; %.1f %% of pixels valid; %.1f %% seen by two or more passes\n", 100.0 * (double)pic.valid_pixels / area, 100.0 * (double)pic.overlap_pixels / area);
+	}
+	if (!code && req->overlay) {
+		snprintf(name, len, "%s_%s_polar", stem, tag);
+		code = polar_overlay_file(name, req->overlay, &pic, wld, prj, device);
+	}
+	free(name);
+	mdemod_polar_free(&pic);
+	return code;
+}
+
+/* --map-proj stereo: the composite (--composite; auto on what the passes received together) or every channel that received a strip
+ * in any pass, of the n passes that gave a picture.  0, or the exit status. */
+static int
+polar_files(const char *stem, const mdemod_image_result *const *results, int n_results, const struct vcdu_req *req, int device)
+{
+	mdemod_polar_pass passes[MDEMOD_POLAR_MAX_PASSES];
+	uint32_t n = 0;
+	int got[3] = { 0, 0, 0 }, code = 0;
+	memset(passes, 0, sizeof passes);
+	for (int i = 0; i < n_results && n < MDEMOD_POLAR_MAX_PASSES; i++) {
+		const mdemod_image_result *res = results[i];
+		const uint32_t rows = res->summary.rows;
+		int any = 0;
+		for (int k = 0; k < 3; k++)
+			for (uint64_t c = 0; c < (uint64_t)rows * MDEMOD_IMAGE_CELLS; c++)
+				if (res->filled[k][c]) { got[k] = any = 1; break; }
+		if (!any) continue;
+		mdemod_polar_pass *p = &passes[n++];
+		p->tle_text = req->tle_text; p->norad = req->norad;
+		p->date = req->date_given ? req->map_date : MDEMOD_POLAR_DATE_AUTO;
+		for (int k = 0; k < 3; k++) { p->image[k] = res->image[k]; p->filled[k] = res->filled[k]; }
+		p->rows = rows; p->place = res->place; p->sinfo = res->sinfo; p->n_desc = res->n_packets;
+	}
+	char tag[16];
+	if (!n) return 0;                                                          /* (no picture: the image layer's line has said so) */
+	if (req->composite) {
+		uint32_t select[3] = { req->comp[0], req->comp[1], req->comp[2] };
+		if (req->composite == 2) {
+			if (got[0] && got[1] && got[2]) { select[0] = 2; select[1] = 1; select[2] = 0; }
+			else if (got[0] && got[1]) { select[0] = 1; select[1] = 1; select[2] = 0; }
+			else return 0;
+		}
+		snprintf(tag, sizeof tag, "%u%u%u", (unsigned)select[0] + 1, (unsigned)select[1] + 1, (unsigned)select[2] + 1);
+		return polar_file(stem, passes, n, req, select, 3, tag, device);
+	}
+	for (int k = 0; k < 3 && !code; k++) {
+		if (!got[k]) continue;
+		const uint32_t select[1] = { (uint32_t)k };
+		snprintf(tag, sizeof tag, "%u", (unsigned)req->apids[k]);
+		code = polar_file(stem, passes, n, req, select, 1, tag, device);
+	}
+	return code;
+}
+
 /* --image: n VCDUs through the image layer, one PGM per active channel that received a strip beside the output file, one line.
  * 0, or the exit status. */
 static int
@@ -1338,7 +1539,13 @@ image_files(const char *s_name, const uint8_t *vcdu, const mdemod_rs_info *info,
 		free(base);
 	}
 	if (!code && (req->rectify || req->composite)) code = picture_files(s_name, &res, req, device);
-	if (!code && req->map) code = map_files(s_name, &res, req, device);
+	if (!code && req->map && req->polar) {
+		const mdemod_image_result *one[1] = { &res };
+		char *stem = beside(s_name, "");
+		if (!stem) { fprintf(stderr, "--map-proj stereo: out of memory\n"); code = 2; }
+		else code = polar_files(stem, one, 1, req, device);
+		free(stem);
+	} else if (!code && req->map) code = map_files(s_name, &res, req, device);
 	if (!code && req->keep) *req->keep = res;                                  /* (the mosaic frees it) */
 	else mdemod_image_free(&res);
 	return code;
@@ -1472,7 +1679,7 @@ main(int argc, char **argv)
 	int auto_offset = 0, auto_decimate = 0, decimate_given = 0, scan = 0, want_cadu = 0, want_vcdu = 0, want_diff = 0, want_skew = 0, want_int = 0, want_image = 0, apids_given = 0, geometry_given = 0, altitude_given = 0, map_opts_given = 0;
 	const char *map_fname = NULL, *mosaic_base = NULL;
 	uint32_t map_norad = 0;
-	int mosaic_blend_given = 0;
+	int mosaic_blend_given = 0, polar_opts_given = 0;
 	struct vcdu_req vreq = { 0, 0, { 64, 65, 66 }, 0, 0, { 2, 1, 0 }, 0.0, 0.0 };
 	/* --overlay: yellow, one pixel, opaque; --graticule: grey, one pixel, opacity 160 */
 	static struct overlay_req oreq = { .style = { { 128, 256, { 255, 255, 0 }, 0 }, { 128, 160, { 128, 128, 128 }, 0 } } };
@@ -1617,6 +1824,29 @@ main(int argc, char **argv)
 			jpeg_req.quality = (unsigned)q;
 			break;
 		}
+		case 0x27:
+			if (!strcmp(optarg, "stereo")) vreq.polar = 1;
+			else if (!strcmp(optarg, "latlon")) vreq.polar = 0;
+			else { fprintf(stderr, "--map-proj: latlon or stereo\n"); return 1; }
+			map_opts_given = 1;
+			break;
+		case 0x28:
+		case 0x29:
+		case 0x2a: {
+			char *end = optarg;
+			const int automatic = c == 0x29 && !strcmp(optarg, "auto");
+			const double v = automatic ? 0.0 : strtod(optarg, &end);
+			if (!automatic && (end == optarg || *end)) { fprintf(stderr, "%s: a number\n", c == 0x28 ? "--map-res" : c == 0x29 ? "--map-lon0" : "--map-lat-ts"); return 1; }
+			if (c == 0x28 && !(v >= MDEMOD_POLAR_MIN_RES && v <= MDEMOD_POLAR_MAX_RES)) { fprintf(stderr, "--map-res: metres per pixel, 100 .. 100000\n"); return 1; }
+			if (c == 0x29 && !automatic && !(v >= -360.0 && v <= 360.0)) { fprintf(stderr, "--map-lon0: degrees, -360 .. 360, or auto\n"); return 1; }
+			if (c == 0x2a && !(v > 0.0 && v <= 90.0)) { fprintf(stderr, "--map-lat-ts: the magnitude of the standard parallel in degrees, 0 < .. <= 90\n"); return 1; }
+			if (c == 0x28) vreq.polar_res = v;
+			else if (c == 0x2a) vreq.polar_lat_ts = v;
+			else { vreq.polar_lon0 = v; vreq.lon0_given = !automatic; }
+			polar_opts_given = 1;
+			map_opts_given = 1;
+			break;
+		}
 		case 0x21:
 			if (!strcmp(optarg, "feather")) vreq.mosaic_blend = MDEMOD_MOSAIC_FEATHER;
 			else if (!strcmp(optarg, "best")) vreq.mosaic_blend = MDEMOD_MOSAIC_BEST;
@@ -1706,6 +1936,18 @@ main(int argc, char **argv)
 		        have_frames() ? "meteor_demod_amd_rs.h" : "meteor_demod_amd_frames.h");
 		return 1;
 	}
+	if (vreq.polar && !(have_polar() && have_map() && have_picture())) {
+		fprintf(stderr, "--map-proj stereo: this library has no polar layer (built without include/meteor_demod_amd_polar.h's entries)\n");
+		return 1;
+	}
+	if (polar_opts_given && !vreq.polar) {
+		fprintf(stderr, "--map-res / --map-lon0 / --map-lat-ts: only with --map-proj stereo (they are its options)\n");
+		return 1;
+	}
+	if (vreq.polar && vreq.map_scale != 0.0) {
+		fprintf(stderr, "--map-scale: not with --map-proj stereo (pixels per degree belong to the latitude / longitude grid: --map-res)\n");
+		return 1;
+	}
 	if (mosaic_base && !(have_mosaic() && have_map() && have_picture())) {
 		fprintf(stderr, "--mosaic: this library has no mosaic layer (built without include/meteor_demod_amd_mosaic.h's entries)\n");
 		return 1;
@@ -1741,7 +1983,7 @@ main(int argc, char **argv)
 		return 1;
 	}
 	if (map_opts_given && !map_fname) {
-		fprintf(stderr, "--norad / --map-scale / --date / --time-offset / --scan-side: only with --map (they are its options)\n");
+		fprintf(stderr, "--norad / --map-scale / --date / --time-offset / --scan-side / --map-proj: only with --map (they are its options)\n");
 		return 1;
 	}
 	if (mosaic_base && !(map_fname && want_image)) {
@@ -2058,7 +2300,14 @@ main(int argc, char **argv)
 			rc_all = cadu_file(io[i].out_name, devs[i % n_dev], want_cadu, &one, want_diff, want_skew, want_int ? (uint32_t)int_delay : 0);
 		}
 	if (mosaic_base) {
-		if (rc_all == 0) rc_all = mosaic_files(mosaic_base, kept, io, n_files, &vreq, devs[0]);
+		if (rc_all == 0 && vreq.polar) {
+			/* (all passes on one polar grid instead of the latitude / longitude mosaic) */
+			const mdemod_image_result *all[MDEMOD_POLAR_MAX_PASSES];
+			for (int i = 0; i < n_files; i++) all[i] = &kept[i];
+			rc_all = polar_files(mosaic_base, all, n_files, &vreq, devs[0]);
+			for (int i = 0; i < n_files; i++) mdemod_image_free(&kept[i]);
+		}
+		else if (rc_all == 0) rc_all = mosaic_files(mosaic_base, kept, io, n_files, &vreq, devs[0]);
 		else for (int i = 0; i < n_files; i++) mdemod_image_free(&kept[i]);
 	}
 	if (jpeg_req.quality && rc_all == 0)

@@ -389,6 +389,23 @@ map_frame_lon_left(const MapFrame &f)
 	return f.left >= 180.0 ? f.left - 360.0 : f.left < -180.0 ? f.left + 360.0 : f.left;
 }
 
+namespace {
+
+/* one node: the source pixel that sees (lat, lon), rounded to 1 / 256 pixel */
+inline void
+put_node(const Inverse &inv, double lat, double lon, int32_t *node)
+{
+	double y, x;
+	node[0] = node[1] = MDEMOD_MAP_NO_NODE;
+	if (!inv.solve(lat, lon, y, x)) return;
+	const double X = floor(256.0 * x + 0.5), Y = floor(256.0 * y + 0.5);
+	if (!(fabs(X) < 2.0e9 && fabs(Y) < 2.0e9)) return;
+	node[0] = static_cast<int32_t>(X);
+	node[1] = static_cast<int32_t>(Y);
+}
+
+} /* namespace */
+
 void
 map_nodes_on(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, uint32_t lines, const MapFrame &f, int32_t *nodes)
 {
@@ -396,16 +413,46 @@ map_nodes_on(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemo
 	const Inverse inv(p, lines, o.scan_deg);
 	const uint32_t node_rows = map_node_count(f.height), node_cols = map_node_count(f.width);
 	for (uint32_t a = 0; a < node_rows; a++)
-		for (uint32_t b = 0; b < node_cols; b++) {
-			int32_t *node = nodes + 2 * (static_cast<size_t>(a) * node_cols + b);
-			double y, x;
-			node[0] = node[1] = MDEMOD_MAP_NO_NODE;
-			if (!inv.solve(f.lat_top - (MAP_STEP * a + 0.5) / f.sy, f.left + (MAP_STEP * b + 0.5) / f.sx, y, x)) continue;
-			const double X = floor(256.0 * x + 0.5), Y = floor(256.0 * y + 0.5);
-			if (!(fabs(X) < 2.0e9 && fabs(Y) < 2.0e9)) continue;
-			node[0] = static_cast<int32_t>(X);
-			node[1] = static_cast<int32_t>(Y);
-		}
+		for (uint32_t b = 0; b < node_cols; b++)
+			put_node(inv, f.lat_top - (MAP_STEP * a + 0.5) / f.sy, f.left + (MAP_STEP * b + 0.5) / f.sx, nodes + 2 * (static_cast<size_t>(a) * node_cols + b));
+}
+
+void
+map_nodes_at(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, uint32_t lines, const double *lat, const double *lon,
+             size_t n, int32_t *nodes)
+{
+	const Pass p = pass_of(tle, tm, o, date);
+	const Inverse inv(p, lines, o.scan_deg);
+	for (size_t k = 0; k < n; k++) {
+		if (std::isfinite(lat[k]) && std::isfinite(lon[k])) put_node(inv, lat[k], lon[k], nodes + 2 * k);
+		else nodes[2 * k] = nodes[2 * k + 1] = MDEMOD_MAP_NO_NODE;
+	}
+}
+
+bool
+map_forward(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, double y, double x, double &lat, double &lon)
+{
+	return forward(pass_of(tle, tm, o, date), y, x, lat, lon);
+}
+
+void
+map_solver_of(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, uint32_t lines, MapSolver &s)
+{
+	const Pass p = pass_of(tle, tm, o, date);
+	Inverse inv(p, lines, o.scan_deg);
+	const double two_pi = 2.0 * MAP_PI;
+	const double dt = (static_cast<double>(date) - static_cast<double>(p.orbit.epoch_day)) * 86400.0 + (inv.table_t0 - p.orbit.epoch_sec);
+	const double d = (static_cast<double>(date) - 10957.0) + (inv.table_t0 - 43200.0) / 86400.0;
+	s.a = p.orbit.a; s.ci = p.orbit.ci; s.si = p.orbit.si;
+	s.raan_dot = p.orbit.raan_dot; s.u_dot = p.orbit.u_dot; s.g_dot = MAP_EARTH_RATE;
+	s.raan_t0 = fmod(p.orbit.raan0 + p.orbit.raan_dot * dt, two_pi);
+	s.u_t0 = fmod(p.orbit.u0 + p.orbit.u_dot * dt, two_pi);
+	s.g_t0 = fmod(280.46061837 + 360.98564736629 * d, 360.0) * MAP_RAD;
+	s.table_t0 = inv.table_t0; s.table_step = MAP_TABLE_STEP;
+	s.sec_lo = inv.sec_lo; s.sec_hi = inv.sec_hi; s.theta_max = inv.theta_max;
+	s.s0 = p.s0; s.line_period = p.line_period; s.offset = p.offset; s.step = p.step;
+	s.side = p.side;
+	s.table.swap(inv.table);
 }
 
 int

@@ -6,6 +6,9 @@
 #ifndef MDEMOD_MAP_HOST_H
 #define MDEMOD_MAP_HOST_H
 
+#include <cstddef>
+#include <vector>
+
 #include "../../include/meteor_demod_amd_map.h"
 #include "picture_host.h"
 
@@ -58,6 +61,20 @@ double map_frame_lon_left(const MapFrame &f);
 /* nodes[map_node_count(f.height)][map_node_count(f.width)][2] of this pass */
 void map_nodes_on(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, uint32_t lines, const MapFrame &f,
                   int32_t *nodes);
+
+/* What other projections (csrc/polar_host.cpp) take from this layer: the nodes of a pass at prescribed points (degrees; a point
+ * that is not finite has no node) by the solver map_nodes_on uses, the forward function of one pixel, and the solver's constants
+ * for a solver elsewhere: the angles of the orbit and of the Earth at the table's start (reduced to one turn) with their rates in
+ * rad/s, the table of r every table_step seconds from table_t0 on, the margins in UTC seconds and in scan angle. */
+void map_nodes_at(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, uint32_t lines, const double *lat,
+                  const double *lon, size_t n, int32_t *nodes);
+bool map_forward(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, double y, double x, double &lat, double &lon);
+struct MapSolver {
+	double a, ci, si, raan_dot, u_dot, g_dot, raan_t0, u_t0, g_t0, table_t0, table_step, sec_lo, sec_hi, theta_max, s0, line_period, offset, step;
+	int side;
+	std::vector<double> table;                   /* [entries][3] */
+};
+void map_solver_of(const mdemod_map_tle &tle, const mdemod_map_timing &tm, const mdemod_map_opts &o, int32_t date, uint32_t lines, MapSolver &s);
 
 extern "C" {
 

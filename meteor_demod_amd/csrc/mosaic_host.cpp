@@ -163,9 +163,18 @@ mosaic_compose_bands(const mdemod_mosaic_opts &o, const mdemod_mosaic_pass *pass
 {
 	memset(out, 0, sizeof *out);
 	mdemod_mosaic_nodes grid;
-	int rc = mdemod_mosaic_grid(&o, passes, n, &grid);
+	const int rc = mdemod_mosaic_grid(&o, passes, n, &grid);
 	if (rc) return rc;
 	struct Keep { mdemod_mosaic_nodes *g; ~Keep() { mdemod_mosaic_grid_free(g); } } keep{ &grid };
+	return mosaic_bands_on(o, passes, n, select, planes, grid, out, backend);
+}
+
+int
+mosaic_bands_on(const mdemod_mosaic_opts &o, const mdemod_mosaic_pass *passes, uint32_t n, const uint32_t *select, uint32_t planes,
+                const mdemod_mosaic_nodes &grid, mdemod_mosaic_result *out, MosaicBackend &backend)
+{
+	int rc;
+	memset(out, 0, sizeof *out);
 	out->width = grid.width; out->height = grid.height; out->planes = planes; out->sx = grid.sx; out->n = n; out->blend = o.blend;
 	out->sy = grid.sy; out->lat_top = grid.lat_top; out->lon_left = grid.lon_left;
 	for (uint32_t k = 0; k < n; k++) {

@@ -42,6 +42,11 @@ struct MosaicBackend {
 int  mosaic_compose_bands(const mdemod_mosaic_opts &o, const mdemod_mosaic_pass *passes, uint32_t n, const uint32_t *select, uint32_t planes,
                           mdemod_mosaic_result *out, MosaicBackend &backend);
 
+/* mosaic_compose_bands behind its grid: tables, bands and counts on a grid that is given (its width, height, node counts, n, timing
+ * and whatever of nodes the backend's begin wants); another projection's grid (csrc/polar_host.cpp) comes in here. */
+int  mosaic_bands_on(const mdemod_mosaic_opts &o, const mdemod_mosaic_pass *passes, uint32_t n, const uint32_t *select, uint32_t planes,
+                     const mdemod_mosaic_nodes &grid, mdemod_mosaic_result *out, MosaicBackend &backend);
+
 extern "C" {
 
 /* the model of mosaic_blend: host memory, the same rule */
