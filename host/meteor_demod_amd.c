@@ -1011,6 +1011,55 @@ write_picture(const char *what, char *name, const uint8_t *pixels, uint32_t widt
 	return 0;
 }
 
+/* got[k] set where slot k of an image result received a strip (several results add up); whether any slot did */
+static int
+slots_received(const mdemod_image_result *res, int got[3])
+{
+	int any = 0;
+	for (int k = 0; k < 3; k++)
+		for (uint64_t c = 0; c < (uint64_t)res->summary.rows * MDEMOD_IMAGE_CELLS; c++)
+			if (res->filled[k][c]) { got[k] = any = 1; break; }
+	return any;
+}
+
+/* The pictures a product makes of the slots that received a strip: with --composite one of three planes (the slots given, or auto:
+ * 321 with strips in all three channels, 221 with strips in the first two), otherwise a grey one per channel.  The next choice into
+ * select, *planes and tag ("321", or the channel's APID); *slot is 0 before the first.  1, 0 after the last, -1 where --composite auto
+ * finds neither. */
+static int
+next_choice(const struct vcdu_req *req, const int got[3], int *slot, uint32_t select[3], uint32_t *planes, char tag[16])
+{
+	if (req->composite) {
+		if (*slot) return 0;
+		*slot = 3;
+		for (int k = 0; k < 3; k++) select[k] = req->comp[k];
+		if (req->composite == 2) {
+			if (got[0] && got[1] && got[2]) { select[0] = 2; select[1] = 1; select[2] = 0; }
+			else if (got[0] && got[1]) { select[0] = 1; select[1] = 1; select[2] = 0; }
+			else return -1;
+		}
+		*planes = 3;
+		snprintf(tag, 16, "%u%u%u", (unsigned)select[0] + 1, (unsigned)select[1] + 1, (unsigned)select[2] + 1);
+		return 1;
+	}
+	while (*slot < 3 && !got[*slot]) (*slot)++;
+	if (*slot >= 3) return 0;
+	select[0] = (uint32_t)*slot;
+	*planes = 1;
+	snprintf(tag, 16, "%u", (unsigned)req->apids[(*slot)++]);
+	return 1;
+}
+
+/* `text` into the file `name`.  `what` is the option the messages begin with, `tail` what a failed write adds.  0, or 1. */
+static int
+write_text(const char *what, const char *name, const char *text, const char *tail)
+{
+	FILE *o = fopen(name, "w");
+	if (!o) { fprintf(stderr, "%s: could not open %s\n", what, name); return 1; }
+	if ((fputs(text, o) < 0) | (fclose(o) != 0)) { fprintf(stderr, "%s: writing %s failed%s\n", what, name, tail); return 1; }
+	return 0;
+}
+
 /* --rectify / --composite: the pictures of one file through the picture layer.  One <apid>_rect.pgm per channel that received a
  * strip (--rectify), one <abc>.ppm and its line (--composite).  0, or the exit status. */
 static int
@@ -1019,8 +1068,7 @@ picture_files(const char *s_name, const mdemod_image_result *res, const struct v
 	const uint32_t rows = res->summary.rows;
 	const uint8_t *image[3] = { res->image[0], res->image[1], res->image[2] }, *filled[3] = { res->filled[0], res->filled[1], res->filled[2] };
 	int got[3] = { 0, 0, 0 }, code = 0;
-	for (int k = 0; k < 3; k++)
-		for (uint64_t c = 0; c < (uint64_t)rows * MDEMOD_IMAGE_CELLS && !got[k]; c++) got[k] = res->filled[k][c];
+	slots_received(res, got);
 	mdemod_picture_opts po;
 	mdemod_picture_default_opts(&po);
 	po.rectify = req->rectify ? 1 : 0;
@@ -1041,28 +1089,25 @@ picture_files(const char *s_name, const mdemod_image_result *res, const struct v
 		mdemod_picture_free(&pic);
 	}
 	if (code || !req->composite) return code;
-	uint32_t select[3] = { req->comp[0], req->comp[1], req->comp[2] };
-	char *base = beside(s_name, "");
-	if (req->composite == 2) {
-		if (got[0] && got[1] && got[2]) { select[0] = 2; select[1] = 1; select[2] = 0; }
-		else if (got[0] && got[1]) { select[0] = 1; select[1] = 1; select[2] = 0; }
-		else {
-			printf("%s: no composite (--composite auto wants strips in all three channels, or in the first two)\n", base ? base : s_name);
-			free(base);
-			return 0;
-		}
+	uint32_t select[3], planes;
+	char tag[16], *base = beside(s_name, "");
+	int slot = 0;
+	if (next_choice(req, got, &slot, select, &planes, tag) < 0) {
+		printf("%s: no composite (--composite auto wants strips in all three channels, or in the first two)\n", base ? base : s_name);
+		free(base);
+		return 0;
 	}
 	mdemod_picture_result pic;
 	const int rc = mdemod_picture_compose_host(&po, image, filled, rows, select, 3, &pic, device);
 	if (rc != MDEMOD_OK) { fprintf(stderr, "--composite: %s: %s\n", s_name, why_of(rc)); free(base); return rc == MDEMOD_ERR_PARAM ? 1 : 2; }
 	char ext[32];
-	snprintf(ext, sizeof ext, "_%u%u%u.ppm", (unsigned)select[0] + 1, (unsigned)select[1] + 1, (unsigned)select[2] + 1);
+	snprintf(ext, sizeof ext, "_%s.ppm", tag);
 	char *name = beside(s_name, ext);
 	if (!name) { fprintf(stderr, "--composite: could not open the picture\n"); code = 1; }
 	else code = write_picture("--composite", name, pic.pixels, pic.width, pic.lines, 3, device);
 	if (!code)
-		printf("%s: composite %u%u%u: %u x %u%s; stretch R %u .. %u, G %u .. %u, B %u .. %u; %.1f %% of pixels valid\n", base ? base : s_name,
-		       (unsigned)select[0] + 1, (unsigned)select[1] + 1, (unsigned)select[2] + 1, pic.width, pic.lines, req->rectify ? " rectified" : "",
+		printf("%s: composite %s: %u x %u%s; stretch R %u .. %u, G %u .. %u, B %u .. %u; %.1f %% of pixels valid\n", base ? base : s_name,
+		       tag, pic.width, pic.lines, req->rectify ? " rectified" : "",
 		       pic.lo[0], pic.hi[0], pic.lo[1], pic.hi[1], pic.lo[2], pic.hi[2],
 		       rows ? 100.0 * (double)pic.valid_cells / ((double)rows * pic.width) : 0.0);
 	free(name); free(base);
@@ -1104,25 +1149,49 @@ map_options(const struct vcdu_req *req, mdemod_map_opts *mo)
 	if (req->side) mo->side = req->side;
 }
 
-/* --overlay / --graticule: a copy of a picture on the grid given with the lines on it: <stem>_overlay.ppm / .pgm, a world file of
- * the picture's six lines and one line on stdout.  0, or the exit status. */
-static int
-overlay_file(const char *stem, const struct overlay_req *ov, uint32_t width, uint32_t height, uint32_t planes, uint32_t sx, double sy, double lat_top, double lon_left,
-             const uint8_t *pixels, const uint8_t *valid, int device)
+/* "yyyy-mm-ddThh:mm:ss.sss" of second `utc0` of day `date` since 1970-01-01 (utc0 may be negative or above 86 400) */
+static void
+utc_text(char out[64], int32_t date, double utc0)
 {
-	const mdemod_overlay_geo geo = { width, height, sx, 0, sy, lat_top, lon_left };
-	mdemod_overlay_vectors grat;
-	mdemod_overlay_layer layers[OVERLAY_FILES + 1];
-	mdemod_overlay_report rep;
-	uint32_t n = 0;
-	memset(&grat, 0, sizeof grat);
-	memset(layers, 0, sizeof layers);
-	if (ov->graticule) {
-		/* (the order of the layers decides no byte: style 0 meets a pixel before style 1) */
-		if (mdemod_overlay_graticule(&geo, ov->step, &grat) != MDEMOD_OK) { fprintf(stderr, "--graticule: %s\n", mdemod_last_error()); return 1; }
-		layers[n].vectors = &grat; layers[n++].style = 1;
+	const double total = (double)date * 86400.0 + utc0, day = floor(total / 86400.0), sec = total - day * 86400.0;
+	int y; unsigned m, d;
+	civil_from_days((int64_t)day, &y, &m, &d);
+	snprintf(out, 64, "%04d-%02u-%02uT%02d:%02d:%06.3f", y, m, d, (int)(sec / 3600.0), (int)(fmod(sec, 3600.0) / 60.0), fmod(sec, 60.0));
+}
+
+/* what follows "first lines" in the line of a picture of n passes: " <time>Z, <time>Z" */
+static void
+print_first_lines(const int32_t *date, const double *utc0, uint32_t n)
+{
+	for (uint32_t k = 0; k < n; k++) {
+		char at[64];
+		utc_text(at, date[k], utc0[k]);
+		printf("%s %sZ", k ? "," : "", at);
 	}
-	for (uint32_t k = 0; k < ov->n_files; k++) { layers[n].vectors = &ov->coast[k]; layers[n++].style = 0; }
+}
+
+/* the six lines of the world file of a latitude / longitude grid */
+static void
+latlon_world_file(char text[160], uint32_t sx, double sy, double lat_top, double lon_left)
+{
+	snprintf(text, 160, "%.17g\n0\n0\n%.17g\n%.17g\n%.17g\n", 1.0 / sx, -1.0 / sy, lon_left + 0.5 / sx, lat_top - 0.5 / sy);
+}
+
+/* one pass of the mosaic or of the polar layer (their structs are field for field alike) from the pictures kept of one file */
+#define PASS_OF(p, res, req, auto_date) do { \
+	(p)->tle_text = (req)->tle_text; (p)->norad = (req)->norad; \
+	(p)->date = (req)->date_given ? (req)->map_date : (auto_date); \
+	for (int k_ = 0; k_ < 3; k_++) { (p)->image[k_] = (res)->image[k_]; (p)->filled[k_] = (res)->filled[k_]; } \
+	(p)->rows = (res)->summary.rows; (p)->place = (res)->place; (p)->sinfo = (res)->sinfo; (p)->n_desc = (res)->n_packets; \
+} while (0)
+
+/* What --overlay / --graticule do alike on every grid: a copy of the picture, draw(lines, copy) on it (the library's code comes
+ * back), <stem>_overlay.ppm / .pgm, and beside it text[t] as <stem>_overlay.<ext[t]> for t < n_text (`tail` as write_text takes
+ * it).  0, or the exit status; the line on stdout is the caller's. */
+static int
+overlay_tail(const char *stem, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t planes, int device, int (*draw)(void *lines, uint8_t *copy), void *lines,
+             const char *const *ext, const char *const *text, int n_text, const char *tail)
+{
 	const size_t bytes = (size_t)height * width * planes, len = strlen(stem) + 32;
 	uint8_t *copy = malloc(bytes ? bytes : 1);
 	char *name = malloc(len);
@@ -1130,28 +1199,66 @@ overlay_file(const char *stem, const struct overlay_req *ov, uint32_t width, uin
 	if (!copy || !name) { fprintf(stderr, "--overlay: out of memory\n"); code = 2; }
 	else {
 		memcpy(copy, pixels, bytes);
-		const int rc = mdemod_overlay_draw_host(&geo, layers, n, ov->style, 2, planes, copy, valid, NULL, 0, &rep, device);
+		const int rc = draw(lines, copy);
 		if (rc != MDEMOD_OK) { fprintf(stderr, "--overlay: %s\n", why_of(rc)); code = rc == MDEMOD_ERR_PARAM ? 1 : 2; }
 	}
 	if (!code) {
 		snprintf(name, len, "%s_overlay.%s", stem, planes == 3 ? "ppm" : "pgm");
 		code = write_picture("--overlay", name, copy, width, height, planes, device);
 	}
-	if (!code) {
-		snprintf(name, len, "%s_overlay.wld", stem);
-		FILE *o = fopen(name, "w");
-		if (!o) { fprintf(stderr, "--overlay: could not open %s\n", name); code = 1; }
-		else {
-			const int short_write = fprintf(o, "%.17g\n0\n0\n%.17g\n%.17g\n%.17g\n", 1.0 / sx, -1.0 / sy, lon_left + 0.5 / sx, lat_top - 0.5 / sy) < 0;
-			if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--overlay: writing %s failed: the world file is incomplete\n", name); code = 1; }
-		}
+	for (int t = 0; t < n_text && !code; t++) {
+		snprintf(name, len, "%s_overlay.%s", stem, ext[t]);
+		code = write_text("--overlay", name, text[t], tail);
 	}
-	if (!code)
-		printf("%s_overlay: %llu pieces kept, %llu tiles touched; lines: %llu pieces, %llu pixels; graticule: %llu pieces, %llu pixels\n", stem,
-		       (unsigned long long)(rep.pieces[0] + rep.pieces[1]), (unsigned long long)rep.tiles, (unsigned long long)rep.pieces[0], (unsigned long long)rep.pixels[0],
-		       (unsigned long long)rep.pieces[1], (unsigned long long)rep.pixels[1]);
 	free(copy);
 	free(name);
+	return code;
+}
+
+/* the lines of --overlay / --graticule on a latitude / longitude grid, as mdemod_overlay_draw_host takes them, and its report */
+struct latlon_lines {
+	mdemod_overlay_geo geo;
+	mdemod_overlay_layer layers[OVERLAY_FILES + 1];
+	uint32_t n, planes;
+	const mdemod_overlay_style *style;
+	const uint8_t *valid;
+	mdemod_overlay_report rep;
+	int device;
+};
+
+static int
+latlon_draw(void *lines, uint8_t *copy)
+{
+	struct latlon_lines *l = lines;
+	return mdemod_overlay_draw_host(&l->geo, l->layers, l->n, l->style, 2, l->planes, copy, l->valid, NULL, 0, &l->rep, l->device);
+}
+
+/* --overlay / --graticule: a copy of a picture on the grid given with the lines on it: <stem>_overlay.ppm / .pgm, a world file of
+ * the picture's six lines and one line on stdout.  0, or the exit status. */
+static int
+overlay_file(const char *stem, const struct overlay_req *ov, uint32_t width, uint32_t height, uint32_t planes, uint32_t sx, double sy, double lat_top, double lon_left,
+             const uint8_t *pixels, const uint8_t *valid, int device)
+{
+	struct latlon_lines l;
+	mdemod_overlay_vectors grat;
+	char wld[160];
+	const char *ext[1] = { "wld" }, *text[1] = { wld };
+	memset(&l, 0, sizeof l);
+	memset(&grat, 0, sizeof grat);
+	l.geo = (mdemod_overlay_geo){ width, height, sx, 0, sy, lat_top, lon_left };
+	l.planes = planes; l.style = ov->style; l.valid = valid; l.device = device;
+	if (ov->graticule) {
+		/* (the order of the layers decides no byte: style 0 meets a pixel before style 1) */
+		if (mdemod_overlay_graticule(&l.geo, ov->step, &grat) != MDEMOD_OK) { fprintf(stderr, "--graticule: %s\n", mdemod_last_error()); return 1; }
+		l.layers[l.n].vectors = &grat; l.layers[l.n++].style = 1;
+	}
+	for (uint32_t k = 0; k < ov->n_files; k++) { l.layers[l.n].vectors = &ov->coast[k]; l.layers[l.n++].style = 0; }
+	latlon_world_file(wld, sx, sy, lat_top, lon_left);
+	const int code = overlay_tail(stem, pixels, width, height, planes, device, latlon_draw, &l, ext, text, 1, ": the world file is incomplete");
+	if (!code)
+		printf("%s_overlay: %llu pieces kept, %llu tiles touched; lines: %llu pieces, %llu pixels; graticule: %llu pieces, %llu pixels\n", stem,
+		       (unsigned long long)(l.rep.pieces[0] + l.rep.pieces[1]), (unsigned long long)l.rep.tiles, (unsigned long long)l.rep.pieces[0],
+		       (unsigned long long)l.rep.pixels[0], (unsigned long long)l.rep.pieces[1], (unsigned long long)l.rep.pixels[1]);
 	mdemod_overlay_vectors_free(&grat);
 	return code;
 }
@@ -1167,7 +1274,7 @@ map_file(const char *s_name, const mdemod_image_result *res, const struct vcdu_r
 	const int rc = mdemod_map_compose_host(&mo, &req->tle, image, filled, res->summary.rows, res->place, res->sinfo, res->n_packets, select, planes, &map, device);
 	if (rc != MDEMOD_OK) { fprintf(stderr, "--map: %s: %s\n", s_name, why_of(rc)); return rc == MDEMOD_ERR_PARAM ? 1 : 2; }
 	int code = 0;
-	char ext[48];
+	char ext[48], wld[160], at[64];
 	snprintf(ext, sizeof ext, "_%s_map.%s", tag, planes == 3 ? "ppm" : "pgm");
 	char *name = beside(s_name, ext), *base = beside(s_name, "");
 	if (!name) { fprintf(stderr, "--map: could not open the picture\n"); code = 1; }
@@ -1175,21 +1282,16 @@ map_file(const char *s_name, const mdemod_image_result *res, const struct vcdu_r
 	free(name);
 	snprintf(ext, sizeof ext, "_%s_map.wld", tag);
 	name = code ? NULL : beside(s_name, ext);
-	FILE *o = name ? fopen(name, "w") : NULL;
-	if (!code && !o) { fprintf(stderr, "--map: could not open %s\n", name ? name : "the world file"); code = 1; }
-	else if (!code) {
-		const int short_write = fprintf(o, "%.17g\n0\n0\n%.17g\n%.17g\n%.17g\n", 1.0 / map.sx, -1.0 / map.sy, map.lon_left + 0.5 / map.sx, map.lat_top - 0.5 / map.sy) < 0;
-		if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--map: writing %s failed: the world file is incomplete\n", name); code = 1; }
-	}
+	latlon_world_file(wld, map.sx, map.sy, map.lat_top, map.lon_left);
+	if (!code && !name) { fprintf(stderr, "--map: could not open the world file\n"); code = 1; }
+	else if (!code) code = write_text("--map", name, wld, ": the world file is incomplete");
 	free(name);
 	if (!code) {
-		const double total = (double)map.timing.date * 86400.0 + map.utc0, day = floor(total / 86400.0), sec = total - day * 86400.0;
-		int y; unsigned m, d;
-		civil_from_days((int64_t)day, &y, &m, &d);
-		printf("%s: map %s: %u x %u at %u x %g px/deg; lat %.4f .. %.4f, lon %.4f .. %.4f; row period %.6f s over %u rows; first line %04d-%02u-%02uT%02d:%02d:%06.3fZ; "
+		utc_text(at, map.timing.date, map.utc0);
+		printf("%s: map %s: %u x %u at %u x %g px/deg; lat %.4f .. %.4f, lon %.4f .. %.4f; row period %.6f s over %u rows; first line %sZ; "
 		       "%.1f %% of pixels valid\n", base ? base : s_name, tag, map.width, map.height, map.sx, map.sy, map.lat_top - map.height / map.sy, map.lat_top,
-		       map.lon_left, map.lon_left + (double)map.width / map.sx, map.timing.row_period, map.timing.rows_fit, y, m, d, (int)(sec / 3600.0),
-		       (int)(fmod(sec, 3600.0) / 60.0), fmod(sec, 60.0), 100.0 * (double)map.valid_pixels / ((double)map.width * map.height));
+		       map.lon_left, map.lon_left + (double)map.width / map.sx, map.timing.row_period, map.timing.rows_fit, at,
+		       100.0 * (double)map.valid_pixels / ((double)map.width * map.height));
 	}
 	free(base);
 	if (!code && req->overlay) {
@@ -1207,27 +1309,12 @@ map_file(const char *s_name, const mdemod_image_result *res, const struct vcdu_r
 static int
 map_files(const char *s_name, const mdemod_image_result *res, const struct vcdu_req *req, int device)
 {
-	const uint32_t rows = res->summary.rows;
-	int got[3] = { 0, 0, 0 }, code = 0;
-	for (int k = 0; k < 3; k++)
-		for (uint64_t c = 0; c < (uint64_t)rows * MDEMOD_IMAGE_CELLS && !got[k]; c++) got[k] = res->filled[k][c];
+	int got[3] = { 0, 0, 0 }, code = 0, slot = 0;
+	uint32_t select[3], planes;
 	char tag[16];
-	if (req->composite) {
-		uint32_t select[3] = { req->comp[0], req->comp[1], req->comp[2] };
-		if (req->composite == 2) {
-			if (got[0] && got[1] && got[2]) { select[0] = 2; select[1] = 1; select[2] = 0; }
-			else if (got[0] && got[1]) { select[0] = 1; select[1] = 1; select[2] = 0; }
-			else return 0;                                                         /* (the composite's own line has said so) */
-		}
-		snprintf(tag, sizeof tag, "%u%u%u", (unsigned)select[0] + 1, (unsigned)select[1] + 1, (unsigned)select[2] + 1);
-		return map_file(s_name, res, req, select, 3, tag, device);
-	}
-	for (int k = 0; k < 3 && !code; k++) {
-		if (!got[k]) continue;
-		const uint32_t select[1] = { (uint32_t)k };
-		snprintf(tag, sizeof tag, "%u", (unsigned)req->apids[k]);
-		code = map_file(s_name, res, req, select, 1, tag, device);
-	}
+	slots_received(res, got);
+	/* (where --composite auto finds nothing the composite's own line has said so) */
+	while (!code && next_choice(req, got, &slot, select, &planes, tag) > 0) code = map_file(s_name, res, req, select, planes, tag, device);
 	return code;
 }
 
@@ -1254,38 +1341,26 @@ mosaic_file(const char *base, const mdemod_mosaic_pass *passes, uint32_t n, cons
 	if (!name) { fprintf(stderr, "--mosaic: could not open the picture\n"); code = 1; }
 	else code = write_picture("--mosaic", name, mos.pixels, mos.width, mos.height, planes, device);
 	if (!code) {
+		char wld[160];
 		snprintf(name, len, "%s_%s_mosaic.wld", base, tag);
-		FILE *o = fopen(name, "w");
-		if (!o) { fprintf(stderr, "--mosaic: could not open %s\n", name); code = 1; }
-		else {
-			const int short_write = fprintf(o, "%.17g\n0\n0\n%.17g\n%.17g\n%.17g\n", 1.0 / mos.sx, -1.0 / mos.sy, mos.lon_left + 0.5 / mos.sx, mos.lat_top - 0.5 / mos.sy) < 0;
-			if ((fclose(o) != 0) | short_write) { fprintf(stderr, "--mosaic: writing %s failed: the world file is incomplete\n", name); code = 1; }
-		}
+		latlon_world_file(wld, mos.sx, mos.sy, mos.lat_top, mos.lon_left);
+		code = write_text("--mosaic", name, wld, ": the world file is incomplete");
 	}
-	free(name);
 	if (!code) {
 		const double area = (double)mos.width * mos.height;
+		int32_t date[MDEMOD_MOSAIC_MAX_PASSES];
+		for (uint32_t k = 0; k < mos.n; k++) date[k] = mos.timing[k].date;
 		printf("%s: mosaic %s (%s): %u x %u at %u x %g px/deg; lat %.4f .. %.4f, lon %.4f .. %.4f; %u passes; first lines", base, tag,
 		       mos.blend == MDEMOD_MOSAIC_BEST ? "best" : "feather", mos.width, mos.height, mos.sx, mos.sy, mos.lat_top - mos.height / mos.sy, mos.lat_top, mos.lon_left,
 		       mos.lon_left + (double)mos.width / mos.sx, mos.n);
-		for (uint32_t k = 0; k < mos.n; k++) {
-			const double total = (double)mos.timing[k].date * 86400.0 + mos.utc0[k], day = floor(total / 86400.0), sec = total - day * 86400.0;
-			int y; unsigned m, d;
-			civil_from_days((int64_t)day, &y, &m, &d);
-			printf("%s %04d-%02u-%02uT%02d:%02d:%06.3fZ", k ? "," : "", y, m, d, (int)(sec / 3600.0), (int)(fmod(sec, 3600.0) / 60.0), fmod(sec, 60.0));
-		}
+		print_first_lines(date, mos.utc0, mos.n);
 		printf("; %.1f %% of pixels valid; %.1f %% seen by two or more passes\n", 100.0 * (double)mos.valid_pixels / area, 100.0 * (double)mos.overlap_pixels / area);
 	}
 	if (!code && req->overlay) {
-		const size_t stem_len = strlen(base) + strlen(tag) + 16;
-		char *stem = malloc(stem_len);
-		if (!stem) { fprintf(stderr, "--overlay: out of memory\n"); code = 2; }
-		else {
-			snprintf(stem, stem_len, "%s_%s_mosaic", base, tag);
-			code = overlay_file(stem, req->overlay, mos.width, mos.height, planes, mos.sx, mos.sy, mos.lat_top, mos.lon_left, mos.pixels, mos.valid, device);
-		}
-		free(stem);
+		snprintf(name, len, "%s_%s_mosaic", base, tag);
+		code = overlay_file(name, req->overlay, mos.width, mos.height, planes, mos.sx, mos.sy, mos.lat_top, mos.lon_left, mos.pixels, mos.valid, device);
 	}
+	free(name);
 	mdemod_mosaic_free(&mos);
 	return code;
 }
@@ -1296,48 +1371,38 @@ static int
 mosaic_files(const char *base, mdemod_image_result *kept, const struct stream_io *io, int n_files, const struct vcdu_req *req, int device)
 {
 	mdemod_mosaic_pass passes[MDEMOD_MOSAIC_MAX_PASSES];
-	uint32_t n = 0;
-	int got[3] = { 0, 0, 0 }, code = 0;
+	uint32_t n = 0, select[3], planes;
+	int got[3] = { 0, 0, 0 }, code = 0, slot = 0, more = 0;
+	char tag[16];
 	memset(passes, 0, sizeof passes);
 	for (int i = 0; i < n_files; i++) {
-		const mdemod_image_result *res = &kept[i];
-		const uint32_t rows = res->summary.rows;
-		int any = 0;
-		for (int k = 0; k < 3; k++)
-			for (uint64_t c = 0; c < (uint64_t)rows * MDEMOD_IMAGE_CELLS; c++)
-				if (res->filled[k][c]) { got[k] = any = 1; break; }
-		if (!any) { fprintf(stderr, "--mosaic: %s gave no picture: left out\n", io[i].in_name); continue; }
-		mdemod_mosaic_pass *p = &passes[n++];
-		p->tle_text = req->tle_text; p->norad = req->norad;
-		p->date = req->date_given ? req->map_date : MDEMOD_MOSAIC_DATE_AUTO;
-		for (int k = 0; k < 3; k++) { p->image[k] = res->image[k]; p->filled[k] = res->filled[k]; }
-		p->rows = rows; p->place = res->place; p->sinfo = res->sinfo; p->n_desc = res->n_packets;
+		if (!slots_received(&kept[i], got)) { fprintf(stderr, "--mosaic: %s gave no picture: left out\n", io[i].in_name); continue; }
+		PASS_OF(&passes[n], &kept[i], req, MDEMOD_MOSAIC_DATE_AUTO);
+		n++;
 	}
-	char tag[16];
 	if (!n) { fprintf(stderr, "--mosaic: no pass gave a picture\n"); code = 1; }
-	else if (req->composite) {
-		uint32_t select[3] = { req->comp[0], req->comp[1], req->comp[2] };
-		int none = 0;
-		if (req->composite == 2) {
-			if (got[0] && got[1] && got[2]) { select[0] = 2; select[1] = 1; select[2] = 0; }
-			else if (got[0] && got[1]) { select[0] = 1; select[1] = 1; select[2] = 0; }
-			else none = 1;
-		}
-		if (none) printf("%s: no mosaic (--composite auto wants strips in all three channels, or in the first two)\n", base);
-		else {
-			snprintf(tag, sizeof tag, "%u%u%u", (unsigned)select[0] + 1, (unsigned)select[1] + 1, (unsigned)select[2] + 1);
-			code = mosaic_file(base, passes, n, req, select, 3, tag, device);
-		}
-	} else {
-		for (int k = 0; k < 3 && !code; k++) {
-			if (!got[k]) continue;
-			const uint32_t select[1] = { (uint32_t)k };
-			snprintf(tag, sizeof tag, "%u", (unsigned)req->apids[k]);
-			code = mosaic_file(base, passes, n, req, select, 1, tag, device);
-		}
-	}
+	while (n && !code && (more = next_choice(req, got, &slot, select, &planes, tag)) > 0) code = mosaic_file(base, passes, n, req, select, planes, tag, device);
+	if (more < 0) printf("%s: no mosaic (--composite auto wants strips in all three channels, or in the first two)\n", base);
 	for (int i = 0; i < n_files; i++) mdemod_image_free(&kept[i]);
 	return code;
+}
+
+/* the lines of --overlay / --graticule on a polar picture, as mdemod_polar_draw_host takes them, and its report */
+struct polar_lines {
+	const mdemod_polar_points *layers[OVERLAY_FILES + 1];
+	uint32_t style_of[OVERLAY_FILES + 1], n;
+	mdemod_polar_style styles[2];
+	const mdemod_polar_result *pic;
+	mdemod_polar_drawn rep;
+	int device;
+};
+
+static int
+polar_draw(void *lines, uint8_t *copy)
+{
+	struct polar_lines *l = lines;
+	const mdemod_polar_frame *f = &l->pic->frame;
+	return mdemod_polar_draw_host(l->layers, l->style_of, l->n, l->styles, 2, f->width, f->height, l->pic->planes, copy, l->pic->valid, &l->rep, l->device);
 }
 
 /* --map-proj stereo with --overlay / --graticule: a copy of a polar picture with the lines on it, <stem>_overlay.ppm / .pgm with the
@@ -1346,57 +1411,36 @@ static int
 polar_overlay_file(const char *stem, const struct overlay_req *ov, const mdemod_polar_result *pic, const char *wld, const char *prj, int device)
 {
 	const mdemod_polar_frame *f = &pic->frame;
+	struct polar_lines l;
 	mdemod_polar_lines grat;
 	mdemod_polar_points pts[OVERLAY_FILES + 1];
-	const mdemod_polar_points *layers[OVERLAY_FILES + 1];
-	uint32_t style_of[OVERLAY_FILES + 1], n = 0;
-	mdemod_polar_style styles[2];
-	mdemod_polar_drawn rep;
+	const char *ext[2] = { "wld", "prj" }, *text[2] = { wld, prj };
 	int code = 0;
+	memset(&l, 0, sizeof l);
 	memset(&grat, 0, sizeof grat);
 	memset(pts, 0, sizeof pts);
-	memset(&rep, 0, sizeof rep);
+	l.pic = pic; l.device = device;
 	for (int s = 0; s < 2; s++) {
-		styles[s].half_width = ov->style[s].half_width; styles[s].opacity = ov->style[s].opacity; styles[s].inside_only = ov->style[s].inside_only;
-		memcpy(styles[s].colour, ov->style[s].colour, 3);
+		l.styles[s].half_width = ov->style[s].half_width; l.styles[s].opacity = ov->style[s].opacity; l.styles[s].inside_only = ov->style[s].inside_only;
+		memcpy(l.styles[s].colour, ov->style[s].colour, 3);
 	}
 	if (ov->graticule) {
-		if (mdemod_polar_graticule(f, ov->step, &grat) != MDEMOD_OK || mdemod_polar_vertices(f, grat.lon, grat.lat, grat.first, grat.n_lines, &pts[n]) != MDEMOD_OK) {
+		if (mdemod_polar_graticule(f, ov->step, &grat) != MDEMOD_OK || mdemod_polar_vertices(f, grat.lon, grat.lat, grat.first, grat.n_lines, &pts[l.n]) != MDEMOD_OK) {
 			fprintf(stderr, "--graticule: %s\n", mdemod_last_error());
 			code = 1;
-		} else { layers[n] = &pts[n]; style_of[n++] = 1; }
+		} else { l.layers[l.n] = &pts[l.n]; l.style_of[l.n++] = 1; }
 	}
 	for (uint32_t k = 0; k < ov->n_files && !code; k++) {
-		if (mdemod_polar_vertices(f, ov->coast[k].lon, ov->coast[k].lat, ov->coast[k].first, ov->coast[k].n_lines, &pts[n]) != MDEMOD_OK) {
+		if (mdemod_polar_vertices(f, ov->coast[k].lon, ov->coast[k].lat, ov->coast[k].first, ov->coast[k].n_lines, &pts[l.n]) != MDEMOD_OK) {
 			fprintf(stderr, "--overlay: %s\n", mdemod_last_error());
 			code = 1;
-		} else { layers[n] = &pts[n]; style_of[n++] = 0; }
+		} else { l.layers[l.n] = &pts[l.n]; l.style_of[l.n++] = 0; }
 	}
-	const size_t bytes = (size_t)f->height * f->width * pic->planes, len = strlen(stem) + 32;
-	uint8_t *copy = malloc(bytes ? bytes : 1);
-	char *name = malloc(len);
-	if (!code && (!copy || !name)) { fprintf(stderr, "--overlay: out of memory\n"); code = 2; }
-	if (!code) {
-		memcpy(copy, pic->pixels, bytes);
-		const int rc = mdemod_polar_draw_host(layers, style_of, n, styles, 2, f->width, f->height, pic->planes, copy, pic->valid, &rep, device);
-		if (rc != MDEMOD_OK) { fprintf(stderr, "--overlay: %s\n", why_of(rc)); code = rc == MDEMOD_ERR_PARAM ? 1 : 2; }
-	}
-	if (!code) {
-		snprintf(name, len, "%s_overlay.%s", stem, pic->planes == 3 ? "ppm" : "pgm");
-		code = write_picture("--overlay", name, copy, f->width, f->height, pic->planes, device);
-	}
-	for (int t = 0; t < 2 && !code; t++) {
-		snprintf(name, len, "%s_overlay.%s", stem, t ? "prj" : "wld");
-		FILE *o = fopen(name, "w");
-		if (!o) { fprintf(stderr, "--overlay: could not open %s\n", name); code = 1; }
-		else if ((fputs(t ? prj : wld, o) < 0) | (fclose(o) != 0)) { fprintf(stderr, "--overlay: writing %s failed\n", name); code = 1; }
-	}
+	if (!code) code = overlay_tail(stem, pic->pixels, f->width, f->height, pic->planes, device, polar_draw, &l, ext, text, 2, "");
 	if (!code)
 		printf("%s_overlay: %llu pieces kept, %llu tiles touched; lines: %llu pieces; graticule: %llu pieces every %g degrees\n", stem,
-		       (unsigned long long)(rep.pieces[0] + rep.pieces[1]), (unsigned long long)rep.tiles, (unsigned long long)rep.pieces[0], (unsigned long long)rep.pieces[1],
-		       grat.step_deg);
-	free(copy);
-	free(name);
+		       (unsigned long long)(l.rep.pieces[0] + l.rep.pieces[1]), (unsigned long long)l.rep.tiles, (unsigned long long)l.rep.pieces[0],
+		       (unsigned long long)l.rep.pieces[1], grat.step_deg);
 	for (uint32_t k = 0; k < OVERLAY_FILES + 1; k++) mdemod_polar_points_free(&pts[k]);
 	mdemod_polar_lines_free(&grat);
 	return code;
@@ -1434,22 +1478,17 @@ polar_file(const char *stem, const mdemod_polar_pass *passes, uint32_t n, const 
 	}
 	for (int t = 0; t < 2 && !code; t++) {
 		snprintf(name, len, "%s_%s_polar.%s", stem, tag, t ? "prj" : "wld");
-		FILE *o = fopen(name, "w");
-		if (!o) { fprintf(stderr, "--map-proj stereo: could not open %s\n", name); code = 1; }
-		else if ((fputs(t ? prj : wld, o) < 0) | (fclose(o) != 0)) { fprintf(stderr, "--map-proj stereo: writing %s failed\n", name); code = 1; }
+		code = write_text("--map-proj stereo", name, t ? prj : wld, "");
 	}
 	if (!code) {
 		const double area = (double)pic.frame.width * pic.frame.height;
+		int32_t date[MDEMOD_POLAR_MAX_PASSES];
+		for (uint32_t k = 0; k < pic.n; k++) date[k] = pic.timing[k].date;
 		printf("%s: polar %s (%s): %u x %u at %g m; %s pole, central meridian %g, true scale at %g; E %.0f .. %.0f, N %.0f .. %.0f; %u pass%s; first lines", stem, tag,
 		       pic.blend == MDEMOD_POLAR_BEST ? "best" : "feather", pic.frame.width, pic.frame.height, pic.frame.res, pic.frame.pole > 0 ? "north" : "south",
 		       pic.frame.lon0_deg, pic.frame.lat_ts_deg, pic.frame.e_left, pic.frame.e_left + pic.frame.width * pic.frame.res,
 		       pic.frame.n_top - pic.frame.height * pic.frame.res, pic.frame.n_top, pic.n, pic.n == 1 ? "" : "es");
-		for (uint32_t k = 0; k < pic.n; k++) {
-			const double total = (double)pic.timing[k].date * 86400.0 + pic.utc0[k], day = floor(total / 86400.0), sec = total - day * 86400.0;
-			int y; unsigned m, d;
-			civil_from_days((int64_t)day, &y, &m, &d);
-			printf("%s %04d-%02u-%02uT%02d:%02d:%06.3fZ", k ? "," : "", y, m, d, (int)(sec / 3600.0), (int)(fmod(sec, 3600.0) / 60.0), fmod(sec, 60.0));
-		}
+		print_first_lines(date, pic.utc0, pic.n);
 		printf("; %.1f %% of pixels valid; %.1f %% seen by two or more passes\n", 100.0 * (double)pic.valid_pixels / area, 100.0 * (double)pic.overlap_pixels / area);
 	}
 	if (!code && req->overlay) {
@@ -1467,41 +1506,17 @@ static int
 polar_files(const char *stem, const mdemod_image_result *const *results, int n_results, const struct vcdu_req *req, int device)
 {
 	mdemod_polar_pass passes[MDEMOD_POLAR_MAX_PASSES];
-	uint32_t n = 0;
-	int got[3] = { 0, 0, 0 }, code = 0;
+	uint32_t n = 0, select[3], planes;
+	int got[3] = { 0, 0, 0 }, code = 0, slot = 0;
+	char tag[16];
 	memset(passes, 0, sizeof passes);
 	for (int i = 0; i < n_results && n < MDEMOD_POLAR_MAX_PASSES; i++) {
-		const mdemod_image_result *res = results[i];
-		const uint32_t rows = res->summary.rows;
-		int any = 0;
-		for (int k = 0; k < 3; k++)
-			for (uint64_t c = 0; c < (uint64_t)rows * MDEMOD_IMAGE_CELLS; c++)
-				if (res->filled[k][c]) { got[k] = any = 1; break; }
-		if (!any) continue;
-		mdemod_polar_pass *p = &passes[n++];
-		p->tle_text = req->tle_text; p->norad = req->norad;
-		p->date = req->date_given ? req->map_date : MDEMOD_POLAR_DATE_AUTO;
-		for (int k = 0; k < 3; k++) { p->image[k] = res->image[k]; p->filled[k] = res->filled[k]; }
-		p->rows = rows; p->place = res->place; p->sinfo = res->sinfo; p->n_desc = res->n_packets;
+		if (!slots_received(results[i], got)) continue;
+		PASS_OF(&passes[n], results[i], req, MDEMOD_POLAR_DATE_AUTO);
+		n++;
 	}
-	char tag[16];
-	if (!n) return 0;                                                          /* (no picture: the image layer's line has said so) */
-	if (req->composite) {
-		uint32_t select[3] = { req->comp[0], req->comp[1], req->comp[2] };
-		if (req->composite == 2) {
-			if (got[0] && got[1] && got[2]) { select[0] = 2; select[1] = 1; select[2] = 0; }
-			else if (got[0] && got[1]) { select[0] = 1; select[1] = 1; select[2] = 0; }
-			else return 0;
-		}
-		snprintf(tag, sizeof tag, "%u%u%u", (unsigned)select[0] + 1, (unsigned)select[1] + 1, (unsigned)select[2] + 1);
-		return polar_file(stem, passes, n, req, select, 3, tag, device);
-	}
-	for (int k = 0; k < 3 && !code; k++) {
-		if (!got[k]) continue;
-		const uint32_t select[1] = { (uint32_t)k };
-		snprintf(tag, sizeof tag, "%u", (unsigned)req->apids[k]);
-		code = polar_file(stem, passes, n, req, select, 1, tag, device);
-	}
+	/* (no picture: the image layer's line has said so; nothing for --composite auto: the composite's has) */
+	while (n && !code && next_choice(req, got, &slot, select, &planes, tag) > 0) code = polar_file(stem, passes, n, req, select, planes, tag, device);
 	return code;
 }
 
@@ -1519,10 +1534,10 @@ image_files(const char *s_name, const uint8_t *vcdu, const mdemod_rs_info *info,
 	if (rc != MDEMOD_OK) { fprintf(stderr, "--image: %s: %s\n", s_name, why_of(rc)); return 2; }
 	int code = 0;
 	const uint32_t rows = res.summary.rows;
+	int got[3] = { 0, 0, 0 };
+	slots_received(&res, got);
 	for (int k = 0; k < 3 && !code; k++) {
-		int any = 0;
-		for (uint64_t c = 0; c < (uint64_t)rows * MDEMOD_IMAGE_CELLS && !any; c++) any = res.filled[k][c];
-		if (!any) continue;
+		if (!got[k]) continue;
 		char ext[32];
 		snprintf(ext, sizeof ext, "_%u.pgm", (unsigned)apids[k]);
 		char *name = beside(s_name, ext);

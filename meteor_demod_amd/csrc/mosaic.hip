@@ -20,8 +20,7 @@
 
 #include <cstring>
 
-#include "mosaic_host.h"
-#include "hip_host.h"
+#include "mosaic_device.h"
 #include "warp_device.h"
 
 #define MOSAIC_THREADS 256
@@ -193,77 +192,78 @@ blend_entry(const char *who, const mdemod_mosaic_source *sources, uint32_t n, co
 	return blend_run(sources, n, select, planes, blend, width, height, out_dev, valid_dev, cover_dev, static_cast<hipStream_t>(hip_stream));
 }
 
-/* the kernel in the whole-mosaic entry: every pass's slots and nodes up once, one band down at a time, on the null stream */
-struct DeviceBackend : MosaicBackend {
-	MdmDevMem mem;
-	uint8_t *d_image[MOSAIC_MAX][3] = {}, *d_filled[MOSAIC_MAX][3] = {}, *d_lut = nullptr, *d_out = nullptr, *d_valid = nullptr, *d_cover = nullptr;
-	int32_t *d_nodes[MOSAIC_MAX] = {};
-	uint32_t *d_hist = nullptr;
-	uint32_t rows[MOSAIC_MAX] = {}, n = 0, width = 0, node_cols = 0, planes = 0;
-	int device;
-	explicit DeviceBackend(int dev) : device(dev) {}
-
-	int begin(const mdemod_mosaic_pass *passes, const mdemod_mosaic_nodes &grid, uint32_t pl, uint32_t piece_lines) override
-	{
-		int rc;
-		n = grid.n; width = grid.width; node_cols = grid.node_cols; planes = pl;
-		const size_t node_words = 2 * static_cast<size_t>(grid.node_rows) * grid.node_cols;
-		for (uint32_t k = 0; k < n; k++) {
-			rows[k] = passes[k].rows;
-			for (int s = 0; s < 3; s++) {
-				if (!passes[k].image[s]) continue;
-				if ((rc = mem.alloc(&d_image[k][s], rows[k] * PIC_LINE_BYTES)) || (rc = mem.alloc(&d_filled[k][s], static_cast<size_t>(rows[k]) * PIC_CELLS))) return rc;
-				HIP_TRY(hipMemcpyAsync(d_image[k][s], passes[k].image[s], rows[k] * PIC_LINE_BYTES, hipMemcpyHostToDevice, nullptr));
-				HIP_TRY(hipMemcpyAsync(d_filled[k][s], passes[k].filled[s], static_cast<size_t>(rows[k]) * PIC_CELLS, hipMemcpyHostToDevice, nullptr));
-			}
-			if ((rc = mem.alloc(&d_nodes[k], node_words))) return rc;
-			HIP_TRY(hipMemcpyAsync(d_nodes[k], grid.nodes[k], node_words * sizeof(int32_t), hipMemcpyHostToDevice, nullptr));
-		}
-		if ((rc = mem.alloc(&d_lut, static_cast<size_t>(MOSAIC_MAX) * 3 * 256)) || (rc = mem.alloc(&d_hist, 3 * 256)) ||
-		    (rc = mem.alloc(&d_out, static_cast<size_t>(piece_lines) * width * planes)) || (rc = mem.alloc(&d_valid, static_cast<size_t>(piece_lines) * width)) ||
-		    (rc = mem.alloc(&d_cover, static_cast<size_t>(piece_lines) * width)))
-			return rc;
-		HIP_TRY(hipStreamSynchronize(nullptr));
-		return MDEMOD_OK;
-	}
-
-	int histogram(uint32_t k, uint32_t *hist) override
-	{
-		const int rc = mdemod_picture_histogram_device(d_image[k], d_filled[k], rows[k], d_hist, device, nullptr);
-		if (rc) return rc;
-		HIP_TRY(hipMemcpyAsync(hist, d_hist, 3 * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
-		HIP_TRY(hipStreamSynchronize(nullptr));
-		return MDEMOD_OK;
-	}
-
-	int tables(const uint8_t *lut, uint32_t pl) override
-	{
-		HIP_TRY(hipMemcpyAsync(d_lut, lut, static_cast<size_t>(n) * pl * 256, hipMemcpyHostToDevice, nullptr));
-		HIP_TRY(hipStreamSynchronize(nullptr));
-		return MDEMOD_OK;
-	}
-
-	int band(const uint32_t *select, uint32_t pl, uint32_t blend, uint32_t node_row, uint32_t height, uint8_t *out, uint8_t *valid, uint8_t *cover) override
-	{
-		mdemod_mosaic_source src[MOSAIC_MAX];
-		memset(src, 0, sizeof src);
-		for (uint32_t k = 0; k < n; k++) {
-			for (int s = 0; s < 3; s++) { src[k].image[s] = d_image[k][s]; src[k].filled[s] = d_filled[k][s]; }
-			src[k].lut = d_lut + static_cast<size_t>(k) * pl * 256;
-			src[k].nodes = d_nodes[k] + 2 * static_cast<size_t>(node_row) * node_cols;
-			src[k].rows = rows[k];
-		}
-		const int rc = blend_run(src, n, select, pl, blend, width, height, d_out, d_valid, d_cover, nullptr);
-		if (rc) return rc;
-		HIP_TRY(hipMemcpyAsync(out, d_out, static_cast<size_t>(height) * width * pl, hipMemcpyDeviceToHost, nullptr));
-		HIP_TRY(hipMemcpyAsync(valid, d_valid, static_cast<size_t>(height) * width, hipMemcpyDeviceToHost, nullptr));
-		HIP_TRY(hipMemcpyAsync(cover, d_cover, static_cast<size_t>(height) * width, hipMemcpyDeviceToHost, nullptr));
-		HIP_TRY(hipStreamSynchronize(nullptr));
-		return MDEMOD_OK;
-	}
-};
-
 } /* namespace */
+
+int
+MosaicDeviceBackend::begin(const mdemod_mosaic_pass *passes, const mdemod_mosaic_nodes &grid, uint32_t pl, uint32_t piece_lines)
+{
+	int rc;
+	n = grid.n; width = grid.width; node_cols = grid.node_cols; planes = pl;
+	node_words = 2 * static_cast<size_t>(grid.node_rows) * grid.node_cols;
+	for (uint32_t k = 0; k < n; k++) {
+		rows[k] = passes[k].rows;
+		for (int s = 0; s < 3; s++) {
+			if (!passes[k].image[s]) continue;
+			if ((rc = mem.alloc(&d_image[k][s], rows[k] * PIC_LINE_BYTES)) || (rc = mem.alloc(&d_filled[k][s], static_cast<size_t>(rows[k]) * PIC_CELLS))) return rc;
+			HIP_TRY(hipMemcpyAsync(d_image[k][s], passes[k].image[s], rows[k] * PIC_LINE_BYTES, hipMemcpyHostToDevice, nullptr));
+			HIP_TRY(hipMemcpyAsync(d_filled[k][s], passes[k].filled[s], static_cast<size_t>(rows[k]) * PIC_CELLS, hipMemcpyHostToDevice, nullptr));
+		}
+		if ((rc = mem.alloc(&d_nodes[k], node_words))) return rc;
+	}
+	if ((rc = nodes_in(grid))) return rc;
+	if ((rc = mem.alloc(&d_lut, static_cast<size_t>(MOSAIC_MAX) * 3 * 256)) || (rc = mem.alloc(&d_hist, 3 * 256)) ||
+	    (rc = mem.alloc(&d_out, static_cast<size_t>(piece_lines) * width * planes)) || (rc = mem.alloc(&d_valid, static_cast<size_t>(piece_lines) * width)) ||
+	    (rc = mem.alloc(&d_cover, static_cast<size_t>(piece_lines) * width)))
+		return rc;
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	return MDEMOD_OK;
+}
+
+int
+MosaicDeviceBackend::nodes_in(const mdemod_mosaic_nodes &grid)
+{
+	for (uint32_t k = 0; k < n; k++) HIP_TRY(hipMemcpyAsync(d_nodes[k], grid.nodes[k], node_words * sizeof(int32_t), hipMemcpyHostToDevice, nullptr));
+	return MDEMOD_OK;
+}
+
+int
+MosaicDeviceBackend::histogram(uint32_t k, uint32_t *hist)
+{
+	const int rc = mdemod_picture_histogram_device(d_image[k], d_filled[k], rows[k], d_hist, device, nullptr);
+	if (rc) return rc;
+	HIP_TRY(hipMemcpyAsync(hist, d_hist, 3 * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	return MDEMOD_OK;
+}
+
+int
+MosaicDeviceBackend::tables(const uint8_t *lut, uint32_t pl)
+{
+	HIP_TRY(hipMemcpyAsync(d_lut, lut, static_cast<size_t>(n) * pl * 256, hipMemcpyHostToDevice, nullptr));
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	return MDEMOD_OK;
+}
+
+/* (the buffers are the backend's own: the public entry's overlap checks have nothing to find) */
+int
+MosaicDeviceBackend::band(const uint32_t *select, uint32_t pl, uint32_t blend, uint32_t node_row, uint32_t height, uint8_t *out, uint8_t *valid, uint8_t *cover)
+{
+	mdemod_mosaic_source src[MOSAIC_MAX];
+	memset(src, 0, sizeof src);
+	for (uint32_t k = 0; k < n; k++) {
+		for (int s = 0; s < 3; s++) { src[k].image[s] = d_image[k][s]; src[k].filled[s] = d_filled[k][s]; }
+		src[k].lut = d_lut + static_cast<size_t>(k) * pl * 256;
+		src[k].nodes = d_nodes[k] + 2 * static_cast<size_t>(node_row) * node_cols;
+		src[k].rows = rows[k];
+	}
+	const int rc = blend_run(src, n, select, pl, blend, width, height, d_out, d_valid, d_cover, nullptr);
+	if (rc) return rc;
+	HIP_TRY(hipMemcpyAsync(out, d_out, static_cast<size_t>(height) * width * pl, hipMemcpyDeviceToHost, nullptr));
+	HIP_TRY(hipMemcpyAsync(valid, d_valid, static_cast<size_t>(height) * width, hipMemcpyDeviceToHost, nullptr));
+	HIP_TRY(hipMemcpyAsync(cover, d_cover, static_cast<size_t>(height) * width, hipMemcpyDeviceToHost, nullptr));
+	HIP_TRY(hipStreamSynchronize(nullptr));
+	return MDEMOD_OK;
+}
 
 extern "C" {
 
@@ -284,7 +284,7 @@ try { MDEMOD_API_ENTER
 	if (rc) return rc;
 	if ((rc = mosaic_check_compose("mdemod_mosaic_compose_host", passes, n, select, planes, out))) return rc;
 	if ((rc = mdm_select_device(device))) return rc;
-	DeviceBackend dev(device);
+	MosaicDeviceBackend dev(device);
 	return mosaic_compose_bands(o, passes, n, select, planes, out, dev);
 } MDEMOD_API_CATCH
 

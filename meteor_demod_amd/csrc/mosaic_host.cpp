@@ -97,6 +97,8 @@ struct ModelBackend : MosaicBackend {
 
 } /* namespace */
 
+std::unique_ptr<MosaicBackend> mosaic_model_backend() { return std::unique_ptr<MosaicBackend>(new ModelBackend); }
+
 int
 mosaic_settings(const mdemod_mosaic_opts *opts, mdemod_mosaic_opts &out)
 {

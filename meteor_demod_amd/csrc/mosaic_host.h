@@ -6,6 +6,8 @@
 #ifndef MDEMOD_MOSAIC_HOST_H
 #define MDEMOD_MOSAIC_HOST_H
 
+#include <memory>
+
 #include "../../include/meteor_demod_amd_mosaic.h"
 #include "map_host.h"
 
@@ -38,6 +40,9 @@ struct MosaicBackend {
 	                 uint8_t *cover) = 0;
 	virtual ~MosaicBackend() {}
 };
+
+/* the model in the kernel's place: host memory, the blend of mdemod_mosaic_model_blend */
+std::unique_ptr<MosaicBackend> mosaic_model_backend();
 
 int  mosaic_compose_bands(const mdemod_mosaic_opts &o, const mdemod_mosaic_pass *passes, uint32_t n, const uint32_t *select, uint32_t planes,
                           mdemod_mosaic_result *out, MosaicBackend &backend);

@@ -175,9 +175,12 @@ draw_run(const mdemod_overlay_piece *pieces_dev, uint64_t n_pieces, const uint32
 	return MDEMOD_OK;
 }
 
-/* the kernel in the whole-picture entry: pieces and bins up once, one band up and down at a time, on the null stream */
+/* the kernel in the whole-picture entries: pieces and bins up once, one band up and down at a time, on the null stream.  The device
+ * is taken when the bands begin: a refusal of the arguments comes first and touches no device. */
 struct DeviceBackend : OverlayBackend {
 	MdmDevMem mem;
+	int device;
+	explicit DeviceBackend(int dev) : device(dev) {}
 	mdemod_overlay_piece *d_pieces = nullptr;
 	uint32_t *d_first = nullptr, *d_items = nullptr;
 	uint8_t *d_pixels = nullptr, *d_valid = nullptr, *d_mask = nullptr;
@@ -186,15 +189,17 @@ struct DeviceBackend : OverlayBackend {
 	uint32_t n_styles = 0, width = 0, planes = 0, tiles_x = 0;
 
 	int begin(const mdemod_overlay_pieces &p, const mdemod_overlay_bins &b, const mdemod_overlay_style *st, uint32_t ns, uint32_t w, uint32_t pl, uint32_t piece_lines,
-	          bool with_valid) override
+	          bool with_valid, bool with_mask) override
 	{
-		int rc;
+		int rc = mdm_select_device(device);
+		if (rc) return rc;
 		styles = st; n_styles = ns; width = w; planes = pl; tiles_x = b.tiles_x; n_pieces = p.n; n_items = b.n_items;
 		const size_t tiles = static_cast<size_t>(b.tiles_x) * b.tiles_y;
 		if ((rc = mem.alloc(&d_pieces, p.n)) || (rc = mem.alloc(&d_first, tiles + 1)) || (rc = mem.alloc(&d_items, b.n_items)) ||
-		    (rc = mem.alloc(&d_pixels, static_cast<size_t>(piece_lines) * w * pl)) || (rc = mem.alloc(&d_mask, static_cast<size_t>(piece_lines) * w)))
+		    (rc = mem.alloc(&d_pixels, static_cast<size_t>(piece_lines) * w * pl)))
 			return rc;
 		if (with_valid && (rc = mem.alloc(&d_valid, static_cast<size_t>(piece_lines) * w))) return rc;
+		if (with_mask && (rc = mem.alloc(&d_mask, static_cast<size_t>(piece_lines) * w))) return rc;
 		if (p.n) HIP_TRY(hipMemcpyAsync(d_pieces, p.piece, p.n * sizeof(mdemod_overlay_piece), hipMemcpyHostToDevice, nullptr));
 		HIP_TRY(hipMemcpyAsync(d_first, b.tile_first, (tiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
 		if (b.n_items) HIP_TRY(hipMemcpyAsync(d_items, b.items, b.n_items * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
@@ -208,16 +213,24 @@ struct DeviceBackend : OverlayBackend {
 		HIP_TRY(hipMemcpyAsync(d_pixels, pixels, area * planes, hipMemcpyHostToDevice, nullptr));
 		if (valid) HIP_TRY(hipMemcpyAsync(d_valid, valid, area, hipMemcpyHostToDevice, nullptr));
 		const int rc = draw_run(d_pieces, n_pieces, d_first + static_cast<size_t>(tile_row) * tiles_x, d_items, n_items, styles, n_styles, width, OVERLAY_TILE * tile_row,
-		                        height, planes, d_pixels, valid ? d_valid : nullptr, d_mask, nullptr);
+		                        height, planes, d_pixels, valid ? d_valid : nullptr, mask ? d_mask : nullptr, nullptr);
 		if (rc) return rc;
 		HIP_TRY(hipMemcpyAsync(pixels, d_pixels, area * planes, hipMemcpyDeviceToHost, nullptr));
-		HIP_TRY(hipMemcpyAsync(mask, d_mask, area, hipMemcpyDeviceToHost, nullptr));
+		if (mask) HIP_TRY(hipMemcpyAsync(mask, d_mask, area, hipMemcpyDeviceToHost, nullptr));
 		HIP_TRY(hipStreamSynchronize(nullptr));
 		return MDEMOD_OK;
 	}
 };
 
 } /* namespace */
+
+int
+overlay_draw_points_device(const mdemod_overlay_points *const *layers, const uint32_t *style_of, uint32_t n_layers, const mdemod_overlay_style *styles, uint32_t n_styles,
+                           uint32_t width, uint32_t height, uint32_t planes, uint8_t *pixels, const uint8_t *valid, mdemod_overlay_report *report, int device)
+{
+	DeviceBackend dev(device);
+	return overlay_draw_points(layers, style_of, n_layers, styles, n_styles, width, height, planes, pixels, valid, nullptr, 0, report, dev);
+}
 
 extern "C" {
 
@@ -258,17 +271,7 @@ int
 mdemod_overlay_draw_host(const mdemod_overlay_geo *geo, const mdemod_overlay_layer *layers, uint32_t n_layers, const mdemod_overlay_style *styles, uint32_t n_styles,
                          uint32_t planes, uint8_t *pixels, const uint8_t *valid, uint8_t *mask, uint32_t piece_lines, mdemod_overlay_report *report, int device)
 try { MDEMOD_API_ENTER
-	/* (the device is taken before the bands begin; a refusal of the arguments comes first and touches no device) */
-	struct Late : DeviceBackend {
-		int device;
-		explicit Late(int d) : device(d) {}
-		int begin(const mdemod_overlay_pieces &p, const mdemod_overlay_bins &b, const mdemod_overlay_style *st, uint32_t ns, uint32_t w, uint32_t pl, uint32_t lines,
-		          bool with_valid) override
-		{
-			const int rc = mdm_select_device(device);
-			return rc ? rc : DeviceBackend::begin(p, b, st, ns, w, pl, lines, with_valid);
-		}
-	} dev(device);
+	DeviceBackend dev(device);
 	return overlay_draw_bands("mdemod_overlay_draw_host", geo, layers, n_layers, styles, n_styles, planes, pixels, valid, mask, piece_lines, report, dev);
 } MDEMOD_API_CATCH
 

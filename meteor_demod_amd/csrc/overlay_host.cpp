@@ -381,7 +381,7 @@ struct ModelBackend : OverlayBackend {
 	const mdemod_overlay_bins *bins = nullptr;
 	const mdemod_overlay_style *styles = nullptr;
 	uint32_t n_styles = 0, width = 0, planes = 0;
-	int begin(const mdemod_overlay_pieces &p, const mdemod_overlay_bins &b, const mdemod_overlay_style *st, uint32_t ns, uint32_t w, uint32_t pl, uint32_t, bool) override
+	int begin(const mdemod_overlay_pieces &p, const mdemod_overlay_bins &b, const mdemod_overlay_style *st, uint32_t ns, uint32_t w, uint32_t pl, uint32_t, bool, bool) override
 	{
 		pieces = &p; bins = &b; styles = st; n_styles = ns; width = w; planes = pl;
 		return MDEMOD_OK;
@@ -426,30 +426,45 @@ overlay_draw_bands(const char *who, const mdemod_overlay_geo *geo, const mdemod_
 		if (!layers[l].vectors) REFUSE("%s: the vectors of layer %u are needed", who, l);
 		if (layers[l].style >= n_styles) REFUSE("%s: layer %u has style %u of %u", who, l, layers[l].style, n_styles);
 	}
-	const uint32_t W = geo->width, H = geo->height, P = piece_lines ? piece_lines : 1024;
+	struct Points : std::vector<mdemod_overlay_points> { ~Points() { for (mdemod_overlay_points &p : *this) mdemod_overlay_points_free(&p); } } pts;
+	pts.resize(n_layers);                                                      /* (zeroed: nothing to free yet) */
+	std::vector<const mdemod_overlay_points *> of(n_layers);
+	std::vector<uint32_t> style_of(n_layers);
+	for (uint32_t l = 0; l < n_layers; l++) {
+		if ((rc = mdemod_overlay_project(geo, layers[l].vectors, &pts[l]))) return rc;
+		of[l] = &pts[l];
+		style_of[l] = layers[l].style;
+	}
+	/* (the report counts pixels in the mask: one of its own where none was asked for) */
+	std::vector<uint8_t> own;
+	if (!mask && report) { own.resize(static_cast<size_t>(geo->height) * geo->width); mask = own.data(); }
+	return overlay_draw_points(of.data(), style_of.data(), n_layers, styles, n_styles, geo->width, geo->height, planes, pixels, valid, mask, piece_lines, report, backend);
+}
+
+int
+overlay_draw_points(const mdemod_overlay_points *const *layers, const uint32_t *style_of, uint32_t n_layers, const mdemod_overlay_style *styles, uint32_t n_styles,
+                    uint32_t W, uint32_t H, uint32_t planes, uint8_t *pixels, const uint8_t *valid, uint8_t *mask, uint32_t piece_lines, mdemod_overlay_report *report,
+                    OverlayBackend &backend)
+{
+	int rc;
+	const uint32_t P = piece_lines ? piece_lines : 1024;
+	if (report) memset(report, 0, sizeof *report);
 	mdemod_overlay_pieces pieces;
 	mdemod_overlay_bins bins;
 	memset(&pieces, 0, sizeof pieces);
 	memset(&bins, 0, sizeof bins);
 	struct Keep { mdemod_overlay_pieces *p; mdemod_overlay_bins *b; ~Keep() { mdemod_overlay_pieces_free(p); mdemod_overlay_bins_free(b); } } keep{ &pieces, &bins };
-	for (uint32_t l = 0; l < n_layers; l++) {
-		mdemod_overlay_points pts;
-		if ((rc = mdemod_overlay_project(geo, layers[l].vectors, &pts))) return rc;
-		rc = mdemod_overlay_cut(&pts, layers[l].style, styles[layers[l].style].half_width, W, H, &pieces);
-		mdemod_overlay_points_free(&pts);
-		if (rc) return rc;
-	}
+	for (uint32_t l = 0; l < n_layers; l++)
+		if ((rc = mdemod_overlay_cut(layers[l], style_of[l], styles[style_of[l]].half_width, W, H, &pieces))) return rc;
 	if ((rc = mdemod_overlay_bin(pieces.piece, pieces.n, styles, n_styles, W, H, &bins))) return rc;
-	std::vector<uint8_t> own;
-	if (!mask) { own.resize(static_cast<size_t>(H) * W); mask = own.data(); }
-	if ((rc = backend.begin(pieces, bins, styles, n_styles, W, planes, P < H ? P : overlay_tiles(H) * OVERLAY_TILE, valid != nullptr))) return rc;
+	if ((rc = backend.begin(pieces, bins, styles, n_styles, W, planes, P < H ? P : overlay_tiles(H) * OVERLAY_TILE, valid != nullptr, mask != nullptr))) return rc;
 	for (uint32_t at = 0; at < H; at += P)
 		if ((rc = backend.band(at / OVERLAY_TILE, P < H - at ? P : H - at, pixels + static_cast<size_t>(at) * W * planes, valid ? valid + static_cast<size_t>(at) * W : nullptr,
-		                       mask + static_cast<size_t>(at) * W)))
+		                       mask ? mask + static_cast<size_t>(at) * W : nullptr)))
 			return rc;
 	if (report) {
 		for (uint64_t k = 0; k < pieces.n; k++) report->pieces[pieces.piece[k].style]++;
-		for (size_t k = 0; k < static_cast<size_t>(H) * W; k++)
+		for (size_t k = 0; mask && k < static_cast<size_t>(H) * W; k++)
 			for (uint32_t s = 0; s < n_styles; s++) report->pixels[s] += (mask[k] >> s) & 1u;
 		for (size_t t = 0; t < static_cast<size_t>(bins.tiles_x) * bins.tiles_y; t++) report->tiles += bins.tile_first[t + 1] > bins.tile_first[t];
 		report->items = bins.n_items;

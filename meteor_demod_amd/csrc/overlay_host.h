@@ -34,18 +34,33 @@ inline uint32_t overlay_tiles(uint32_t pixels) { return (pixels + OVERLAY_TILE -
 int  overlay_check_draw(const char *who, const mdemod_overlay_style *styles, uint32_t n_styles, uint32_t width, uint32_t height, uint32_t planes,
                         const void *pixels, const void *valid);
 
-/* what stands in the kernel's place in the whole-picture entry.  begin: the pieces and the bins of the whole picture; band: the
- * lines from tile row `tile_row` on, `height` of them, in host memory, drawn in place.  Synchronous. */
+/* what stands in the kernel's place in the whole-picture entry.  begin: the pieces and the bins of the whole picture, and whether the
+ * bands come with valid and want a mask; band: the lines from tile row `tile_row` on, `height` of them, in host memory, drawn in
+ * place.  Synchronous. */
 struct OverlayBackend {
 	virtual int begin(const mdemod_overlay_pieces &pieces, const mdemod_overlay_bins &bins, const mdemod_overlay_style *styles, uint32_t n_styles, uint32_t width,
-	                  uint32_t planes, uint32_t piece_lines, bool with_valid) = 0;
+	                  uint32_t planes, uint32_t piece_lines, bool with_valid, bool with_mask) = 0;
 	virtual int band(uint32_t tile_row, uint32_t height, uint8_t *pixels, const uint8_t *valid, uint8_t *mask) = 0;
 	virtual ~OverlayBackend() {}
 };
 
+/* the whole-picture entries up to where the projection ends: the argument checks and every layer's vectors to fixed point; then
+ * overlay_draw_points */
 int  overlay_draw_bands(const char *who, const mdemod_overlay_geo *geo, const mdemod_overlay_layer *layers, uint32_t n_layers, const mdemod_overlay_style *styles,
                         uint32_t n_styles, uint32_t planes, uint8_t *pixels, const uint8_t *valid, uint8_t *mask, uint32_t piece_lines,
                         mdemod_overlay_report *report, OverlayBackend &backend);
+
+/* and from there on, for points in fixed point whatever projection made them (csrc/polar.hip): layer l is cut with style style_of[l],
+ * the pieces are binned, the picture goes through the backend in bands of piece_lines lines (0: 1024), the report is filled.  The
+ * arguments were checked (overlay_check_draw, style_of below n_styles, piece_lines a multiple of 32); mask and report may be NULL, and
+ * without a mask the report's pixels stay 0. */
+int  overlay_draw_points(const mdemod_overlay_points *const *layers, const uint32_t *style_of, uint32_t n_layers, const mdemod_overlay_style *styles, uint32_t n_styles,
+                         uint32_t width, uint32_t height, uint32_t planes, uint8_t *pixels, const uint8_t *valid, uint8_t *mask, uint32_t piece_lines,
+                         mdemod_overlay_report *report, OverlayBackend &backend);
+/* overlay_draw_points with the kernel of csrc/overlay.hip as the backend; the device is taken when the bands begin */
+int  overlay_draw_points_device(const mdemod_overlay_points *const *layers, const uint32_t *style_of, uint32_t n_layers, const mdemod_overlay_style *styles,
+                                uint32_t n_styles, uint32_t width, uint32_t height, uint32_t planes, uint8_t *pixels, const uint8_t *valid, mdemod_overlay_report *report,
+                                int device);
 
 extern "C" {
 

@@ -1,7 +1,8 @@
 /*
  * polar.hip — the polar layer on the GPU (include/meteor_demod_amd_polar.h): polar_nodes, and the public entries around it.  The
- * picture itself is made by the mosaic layer's blend kernel through its exported entry (mdemod_mosaic_blend_device); there is no
- * second warp or blend here.
+ * picture itself is made by the mosaic layer's blend kernel through that layer's own device backend (csrc/mosaic_device.h), and the
+ * lines are drawn by the overlay layer's banded draw (csrc/overlay_host.h: overlay_draw_points_device); there is no second warp,
+ * blend or draw here.
  *
  * polar_nodes: one thread per node, blockIdx.y the pass, all passes in one launch.  Everything is double: the node's (E, N) through
  *   the inverse projection (csrc/polar_proj.h, the host's own formulas) to (phi, lam), the geodetic point G, the seed from the
@@ -22,8 +23,8 @@
 #include <vector>
 
 #include "polar_host.h"
-#include "hip_host.h"
-#include "../../include/meteor_demod_amd_overlay.h"
+#include "mosaic_device.h"
+#include "overlay_host.h"
 
 #define POLAR_THREADS   256
 #define POLAR_RE        6378.137                        /* km: the map layer's constants */
@@ -177,81 +178,19 @@ nodes_run(const mdemod_polar_frame &f, const mdemod_polar_solver *solvers, uint3
 	return MDEMOD_OK;
 }
 
-/* the whole-picture entry: every pass's slots up once, the nodes made here (or brought up), one band down at a time through the
- * mosaic layer's blend entry, on the null stream */
-struct DeviceBackend : MosaicBackend {
-	MdmDevMem mem;
-	uint8_t *d_image[POLAR_MAX][3] = {}, *d_filled[POLAR_MAX][3] = {}, *d_lut = nullptr, *d_out = nullptr, *d_valid = nullptr, *d_cover = nullptr, *d_work = nullptr;
-	int32_t *d_nodes[POLAR_MAX] = {};
-	uint32_t *d_hist = nullptr;
-	uint32_t rows[POLAR_MAX] = {}, n = 0, width = 0, node_cols = 0, planes = 0;
-	size_t node_words = 0;
+/* the whole-picture entry: the mosaic layer's backend (csrc/mosaic_device.h: slots up once, tables, one band down at a time through
+ * its blend) with the nodes made on the device, in the backend's own memory, unless they come from the host */
+struct DeviceBackend : MosaicDeviceBackend {
 	const mdemod_polar_nodes &polar;
 	bool on_host;
-	int device;
-	DeviceBackend(int dev, const mdemod_polar_nodes &grid, bool host_nodes) : polar(grid), on_host(host_nodes), device(dev) {}
+	DeviceBackend(int dev, const mdemod_polar_nodes &grid, bool host_nodes) : MosaicDeviceBackend(dev), polar(grid), on_host(host_nodes) {}
 
-	int begin(const mdemod_mosaic_pass *passes, const mdemod_mosaic_nodes &grid, uint32_t pl, uint32_t piece_lines) override
+	int nodes_in(const mdemod_mosaic_nodes &grid) override
 	{
-		int rc;
-		n = grid.n; width = grid.width; node_cols = grid.node_cols; planes = pl;
-		node_words = 2 * static_cast<size_t>(grid.node_rows) * grid.node_cols;
-		for (uint32_t k = 0; k < n; k++) {
-			rows[k] = passes[k].rows;
-			for (int s = 0; s < 3; s++) {
-				if (!passes[k].image[s]) continue;
-				if ((rc = mem.alloc(&d_image[k][s], rows[k] * PIC_LINE_BYTES)) || (rc = mem.alloc(&d_filled[k][s], static_cast<size_t>(rows[k]) * PIC_CELLS))) return rc;
-				HIP_TRY(hipMemcpyAsync(d_image[k][s], passes[k].image[s], rows[k] * PIC_LINE_BYTES, hipMemcpyHostToDevice, nullptr));
-				HIP_TRY(hipMemcpyAsync(d_filled[k][s], passes[k].filled[s], static_cast<size_t>(rows[k]) * PIC_CELLS, hipMemcpyHostToDevice, nullptr));
-			}
-			if ((rc = mem.alloc(&d_nodes[k], node_words))) return rc;
-			if (on_host) HIP_TRY(hipMemcpyAsync(d_nodes[k], grid.nodes[k], node_words * sizeof(int32_t), hipMemcpyHostToDevice, nullptr));
-		}
-		if (!on_host) {
-			if ((rc = mem.alloc(&d_work, static_cast<size_t>(mdemod_polar_nodes_work_bytes(polar.solver, n))))) return rc;
-			if ((rc = nodes_run(polar.frame, polar.solver, n, d_nodes, d_work, nullptr))) return rc;
-		}
-		if ((rc = mem.alloc(&d_lut, static_cast<size_t>(POLAR_MAX) * 3 * 256)) || (rc = mem.alloc(&d_hist, 3 * 256)) ||
-		    (rc = mem.alloc(&d_out, static_cast<size_t>(piece_lines) * width * planes)) || (rc = mem.alloc(&d_valid, static_cast<size_t>(piece_lines) * width)) ||
-		    (rc = mem.alloc(&d_cover, static_cast<size_t>(piece_lines) * width)))
-			return rc;
-		HIP_TRY(hipStreamSynchronize(nullptr));
-		return MDEMOD_OK;
-	}
-
-	int histogram(uint32_t k, uint32_t *hist) override
-	{
-		const int rc = mdemod_picture_histogram_device(d_image[k], d_filled[k], rows[k], d_hist, device, nullptr);
-		if (rc) return rc;
-		HIP_TRY(hipMemcpyAsync(hist, d_hist, 3 * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
-		HIP_TRY(hipStreamSynchronize(nullptr));
-		return MDEMOD_OK;
-	}
-
-	int tables(const uint8_t *lut, uint32_t pl) override
-	{
-		HIP_TRY(hipMemcpyAsync(d_lut, lut, static_cast<size_t>(n) * pl * 256, hipMemcpyHostToDevice, nullptr));
-		HIP_TRY(hipStreamSynchronize(nullptr));
-		return MDEMOD_OK;
-	}
-
-	int band(const uint32_t *select, uint32_t pl, uint32_t blend, uint32_t node_row, uint32_t height, uint8_t *out, uint8_t *valid, uint8_t *cover) override
-	{
-		mdemod_mosaic_source src[POLAR_MAX];
-		memset(src, 0, sizeof src);
-		for (uint32_t k = 0; k < n; k++) {
-			for (int s = 0; s < 3; s++) { src[k].image[s] = d_image[k][s]; src[k].filled[s] = d_filled[k][s]; }
-			src[k].lut = d_lut + static_cast<size_t>(k) * pl * 256;
-			src[k].nodes = d_nodes[k] + 2 * static_cast<size_t>(node_row) * node_cols;
-			src[k].rows = rows[k];
-		}
-		const int rc = mdemod_mosaic_blend_device(src, n, select, pl, blend, width, height, d_out, d_valid, d_cover, device, nullptr);
-		if (rc) return rc;
-		HIP_TRY(hipMemcpyAsync(out, d_out, static_cast<size_t>(height) * width * pl, hipMemcpyDeviceToHost, nullptr));
-		HIP_TRY(hipMemcpyAsync(valid, d_valid, static_cast<size_t>(height) * width, hipMemcpyDeviceToHost, nullptr));
-		HIP_TRY(hipMemcpyAsync(cover, d_cover, static_cast<size_t>(height) * width, hipMemcpyDeviceToHost, nullptr));
-		HIP_TRY(hipStreamSynchronize(nullptr));
-		return MDEMOD_OK;
+		if (on_host) return MosaicDeviceBackend::nodes_in(grid);
+		uint8_t *d_work = nullptr;
+		const int rc = mem.alloc(&d_work, static_cast<size_t>(mdemod_polar_nodes_work_bytes(polar.solver, n)));
+		return rc ? rc : nodes_run(polar.frame, polar.solver, n, d_nodes, d_work, nullptr);
 	}
 
 	/* the nodes the picture was made through, for the result */
@@ -319,43 +258,21 @@ try { MDEMOD_API_ENTER
 	if (!pixels) REFUSE("%s: the picture is needed", who);
 	if (planes != 1 && planes != 3) REFUSE("%s: %u planes (1 or 3)", who, planes);
 	const mdemod_overlay_style *st = reinterpret_cast<const mdemod_overlay_style *>(styles);
-	mdemod_overlay_pieces pieces;
-	mdemod_overlay_bins bins;
-	memset(&pieces, 0, sizeof pieces);
-	memset(&bins, 0, sizeof bins);
-	struct Keep { mdemod_overlay_pieces *p; mdemod_overlay_bins *b; ~Keep() { mdemod_overlay_pieces_free(p); mdemod_overlay_bins_free(b); } } keep{ &pieces, &bins };
-	int rc;
+	int rc = overlay_check_draw(who, st, n_styles, width, height, planes, pixels, valid);
+	if (rc) return rc;
 	for (uint32_t l = 0; l < n_layers; l++) {
 		if (!layers[l]) REFUSE("%s: layer %u is missing", who, l);
 		if (style_of[l] >= n_styles) REFUSE("%s: layer %u has style %u of %u", who, l, style_of[l], n_styles);
-		const uint64_t before = pieces.n;
-		if ((rc = mdemod_overlay_cut(reinterpret_cast<const mdemod_overlay_points *>(layers[l]), style_of[l], st[style_of[l]].half_width, width, height, &pieces))) return rc;
-		if (report) report->pieces[style_of[l]] += pieces.n - before;
 	}
-	if ((rc = mdemod_overlay_bin(pieces.piece, pieces.n, st, n_styles, width, height, &bins))) return rc;
-	const uint64_t tiles = static_cast<uint64_t>(bins.tiles_x) * bins.tiles_y;
+	mdemod_overlay_report drawn;
+	if ((rc = overlay_draw_points_device(reinterpret_cast<const mdemod_overlay_points *const *>(layers), style_of, n_layers, st, n_styles, width, height, planes, pixels, valid,
+	                                     &drawn, device)))
+		return rc;
 	if (report) {
-		report->items = bins.n_items;
-		for (uint64_t t = 0; t < tiles; t++) report->tiles += bins.tile_first[t + 1] != bins.tile_first[t];
+		memcpy(report->pieces, drawn.pieces, sizeof report->pieces);
+		report->tiles = drawn.tiles;
+		report->items = drawn.items;
 	}
-	if ((rc = mdm_select_device(device))) return rc;
-	MdmDevMem mem;
-	mdemod_overlay_piece *d_pieces = nullptr;
-	uint32_t *d_first = nullptr, *d_items = nullptr;
-	uint8_t *d_pixels = nullptr, *d_valid = nullptr;
-	const size_t area = static_cast<size_t>(height) * width;
-	if ((rc = mem.alloc(&d_pieces, pieces.n)) || (rc = mem.alloc(&d_first, tiles + 1)) || (rc = mem.alloc(&d_items, bins.n_items)) || (rc = mem.alloc(&d_pixels, area * planes)) ||
-	    (valid && (rc = mem.alloc(&d_valid, area))))
-		return rc;
-	if (pieces.n) HIP_TRY(hipMemcpyAsync(d_pieces, pieces.piece, pieces.n * sizeof *d_pieces, hipMemcpyHostToDevice, nullptr));
-	HIP_TRY(hipMemcpyAsync(d_first, bins.tile_first, (tiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
-	if (bins.n_items) HIP_TRY(hipMemcpyAsync(d_items, bins.items, bins.n_items * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
-	if (area) HIP_TRY(hipMemcpyAsync(d_pixels, pixels, area * planes, hipMemcpyHostToDevice, nullptr));
-	if (valid && area) HIP_TRY(hipMemcpyAsync(d_valid, valid, area, hipMemcpyHostToDevice, nullptr));
-	if ((rc = mdemod_overlay_draw_device(d_pieces, pieces.n, d_first, d_items, bins.n_items, st, n_styles, width, height, planes, d_pixels, d_valid, nullptr, device, nullptr)))
-		return rc;
-	if (area) HIP_TRY(hipMemcpyAsync(pixels, d_pixels, area * planes, hipMemcpyDeviceToHost, nullptr));
-	HIP_TRY(hipStreamSynchronize(nullptr));
 	return MDEMOD_OK;
 } MDEMOD_API_CATCH
 

@@ -52,35 +52,6 @@ saturated(double v)
 	return !(r > -2147483648.0) ? INT32_MIN : r > 2147483647.0 ? INT32_MAX : static_cast<int32_t>(r);
 }
 
-/* the mosaic layer's model in the kernel's place */
-struct ModelBackend : MosaicBackend {
-	mdemod_mosaic_source src[POLAR_MAX];
-	uint32_t n = 0, width = 0, nc = 0;
-	int begin(const mdemod_mosaic_pass *passes, const mdemod_mosaic_nodes &grid, uint32_t, uint32_t) override
-	{
-		n = grid.n; width = grid.width; nc = grid.node_cols;
-		memset(src, 0, sizeof src);
-		for (uint32_t k = 0; k < n; k++) {
-			for (int s = 0; s < 3; s++) { src[k].image[s] = passes[k].image[s]; src[k].filled[s] = passes[k].filled[s]; }
-			src[k].nodes = grid.nodes[k];
-			src[k].rows = passes[k].rows;
-		}
-		return MDEMOD_OK;
-	}
-	int histogram(uint32_t k, uint32_t *hist) override { return mdemod_picture_model_histogram(src[k].image, src[k].filled, src[k].rows, hist); }
-	int tables(const uint8_t *t, uint32_t planes) override
-	{
-		for (uint32_t k = 0; k < n; k++) src[k].lut = t + static_cast<size_t>(k) * planes * 256;
-		return MDEMOD_OK;
-	}
-	int band(const uint32_t *select, uint32_t planes, uint32_t blend, uint32_t node_row, uint32_t height, uint8_t *out, uint8_t *valid, uint8_t *cover) override
-	{
-		mdemod_mosaic_source at[POLAR_MAX];
-		for (uint32_t k = 0; k < n; k++) { at[k] = src[k]; at[k].nodes += 2 * static_cast<size_t>(node_row) * nc; }
-		return mdemod_mosaic_model_blend(at, n, select, planes, blend, width, height, out, valid, cover);
-	}
-};
-
 int
 check_proj(const char *who, int32_t pole, double lat_ts_deg, double lon0_deg)
 {
@@ -480,8 +451,7 @@ try { MDEMOD_API_ENTER
 	if ((rc = polar_grid_make("mdemod_polar_model_host", o, passes, n, nullptr, true, &grid))) return rc;
 	struct Keep { mdemod_polar_nodes *g; ~Keep() { mdemod_polar_grid_free(g); } } keep{ &grid };
 	o.nodes_on_host = 1;
-	ModelBackend model;
-	return polar_compose(o, passes, n, select, planes, grid, out, model);
+	return polar_compose(o, passes, n, select, planes, grid, out, *mosaic_model_backend());
 } MDEMOD_API_CATCH
 
 int

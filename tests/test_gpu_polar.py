@@ -1,7 +1,7 @@
 """GPU tests of the polar layer (include/meteor_demod_amd_polar.h): the node kernel against the host solver by the header's rule of
 agreement, inside canaries and with its inputs unchanged, on frames from 1 x 1 pixel to the pass over the pole, both hemispheres and
 1, 3 and 8 passes in one launch; the whole entry against the host path byte for byte, in bands, grey and colour, feather and best;
-the device entry's argument checks.  Every GPU step runs once; every test prints the figures it asserts on."""
+the device entry's argument checks; polar.draw against the overlay layer's model byte for byte across a band border.  Every GPU step runs once; every test prints the figures it asserts on."""
 from __future__ import annotations
 
 import ctypes as C
@@ -282,3 +282,48 @@ def test_bands_equal_one_batch(gpu_device):
         print(f"bands of {piece} lines over {whole.height}: equal to one batch: {_same(banded, whole)}")
         assert _same(banded, whole) and np.array_equal(banded.nodes, whole.nodes)
     assert _same(composed((1,), "best", 2, 1, 16), composed((1,), "best", 2, 1))
+
+
+# ------------------------------------------------------------------------------------------------------------------ lines
+DRAW_W, DRAW_H = 36, 1060                            # a multiple of 4 and none of the 32-pixel tile; the band border at line 1024 inside
+DRAW_STYLES = [(128, 256, (255, 0, 0), False), (64, 160, (0, 255, 0), False), (2048, 200, (0, 0, 255), False), (300, 256, (255, 255, 0), True)]
+
+
+def _line(*points):
+    """One polyline through pixel coordinates as (x, y, first) in fixed point."""
+    x, y = (np.rint(256.0 * np.array(c, dtype=np.float64)).astype(np.int32) for c in zip(*points))
+    return x, y, np.array([0, len(points)], dtype=np.uint32)
+
+
+@functools.lru_cache(maxsize=None)
+def draw_layers():
+    """((x, y, first), style): a diagonal across lines 1023 / 1024, a vertical line on the tile edge x = 31.5, a wide line whose square
+    cap reaches across the band border, an inside_only line, and a layer without a line."""
+    none = (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(1, np.uint32))
+    return ((_line((2, 1000), (33, 1050)), 0), (_line((31.5, 10), (31.5, 1055)), 1), (_line((5, 1016), (20, 1021)), 2), (_line((0, 500), (35, 540)), 3), (none, 0))
+
+
+@pytest.mark.parametrize("planes", [3, 1])
+def test_draw_is_the_overlay_layers_model(planes, gpu_device):
+    """polar.draw goes through the overlay layer's banded draw: the bytes are those of that layer's model over the pieces of every
+    layer in layer order, the report's pieces those counted per style, its tiles and items those of the overlay layer's bins."""
+    from meteor_demod_amd import overlay as OV, polar as P
+    rng = np.random.default_rng(17 + planes)
+    pixels = rng.integers(0, 256, (DRAW_H, DRAW_W, 3) if planes == 3 else (DRAW_H, DRAW_W), dtype=np.uint8)
+    valid = (rng.random((DRAW_H, DRAW_W)) >= 0.3).astype(np.uint8)              # holes for the inside_only style
+    styles = [OV.Style(*s) for s in DRAW_STYLES]
+    pcs = np.concatenate([OV.pieces(OV.Points(*pts), s, DRAW_STYLES[s][0], DRAW_W, DRAW_H) for pts, s in draw_layers()])
+    want, mask = OV.model_pieces(pixels, pcs, styles, valid)
+    tile_first, items = OV.bins(pcs, styles, DRAW_W, DRAW_H)
+    got, rep = P.draw(pixels, list(draw_layers()), DRAW_STYLES, valid=valid, device=gpu_device)
+    counts = [int((pcs["style"] == s).sum()) for s in range(4)]
+    changed = (got != pixels).reshape(DRAW_H, DRAW_W, -1).any(axis=-1)
+    print(f"{planes} planes: {len(pcs)} pieces {counts}, report {rep}; {int(changed.sum())} pixels changed, {int(changed[1024:].sum())} of them below the band border, "
+          f"{int((mask != 0).sum())} in the model's mask")
+    assert np.array_equal(got, want)
+    assert rep["pieces"] == counts and all(counts) and rep["tiles"] == int((np.diff(tile_first.astype(np.int64)) > 0).sum()) and rep["items"] == items.size
+    assert changed[:1024].any() and changed[1024:].any() and changed[1023].any() and changed[1024].any()
+    assert (mask == 8).any() and (valid == 0).any() and not (mask & 8)[valid == 0].any()       # the inside_only line keeps out of the holes
+    # no layer at all: the picture comes back unchanged
+    same, none = P.draw(pixels, [], DRAW_STYLES, valid=valid, device=gpu_device)
+    assert np.array_equal(same, pixels) and none == dict(pieces=[0, 0, 0, 0], tiles=0, items=0)

@@ -431,7 +431,10 @@ def test_polar_int_entries_are_function_try_blocks():
     host = (ROOT / "meteor_demod_amd" / "csrc" / "polar_host.cpp").read_text() + listed + (ROOT / "meteor_demod_amd" / "csrc" / "polar_proj.h").read_text()
     assert "hip_runtime" not in host and "hip_host.h" not in host and "map_nodes_at" in host
     device = (ROOT / "meteor_demod_amd" / "csrc" / "polar.hip").read_text()
-    assert "mdemod_mosaic_blend_device" in device and device.count("__global__") == 1
+    # the picture goes through the mosaic layer's own back ends: one kernel here, no band, table or histogram step of its own
+    assert '#include "mosaic_device.h"' in device and device.count("__global__") == 1
+    assert not re.search(r"\b(histogram|tables|band)\(", device)
+    assert not re.search(r":\s*(public\s+)?MosaicBackend\b", (ROOT / "meteor_demod_amd" / "csrc" / "polar_host.cpp").read_text())
 
 
 def test_cli_without_polar_layer_links_and_refuses(tmp_path):
