@@ -70,6 +70,10 @@
  * --map-res <metres>, --map-lon0 <deg|auto>, --map-lat-ts <deg>.  Without it nothing changes.  Weak references.
  * --jpeg <quality> changes the format of every picture above (include/meteor_demod_amd_jpeg.h): a baseline JPEG encoded on the GPU,
  * <same name>.jpg instead of .pgm / .ppm, one line per file and one at the end.  Only with --image.  Weak references.
+ * --equalise <clip> gives every derived picture (_rect, the composite, _map, _mosaic, _polar) local contrast on the GPU
+ * (include/meteor_demod_amd_equalise.h: CLAHE under the picture's own mask) in place, after it is composed and before lines are drawn on
+ * its copy or it is written; --equalise-tile <pixels>, --equalise-amount <percent>; one line per picture.  The channel pictures stay as
+ * decoded.  Only with --image and --rectify, --composite or --map.  Weak references.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -99,6 +103,7 @@
 #include "meteor_demod_amd_polar.h"
 #include "meteor_demod_amd_overlay.h"
 #include "meteor_demod_amd_jpeg.h"
+#include "meteor_demod_amd_equalise.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
 #endif
@@ -138,7 +143,7 @@ static const struct option longopts[] = {
 	{ "time-offset", 1, NULL, 0x1e }, { "scan-side", 1, NULL, 0x1f }, { "mosaic", 1, NULL, 0x20 },   { "mosaic-blend", 1, NULL, 0x21 },
 	{ "overlay", 1, NULL, 0x22 },   { "graticule", 1, NULL, 0x23 }, { "overlay-colour", 1, NULL, 0x24 }, { "overlay-width", 1, NULL, 0x25 },
 	{ "jpeg", 1, NULL, 0x26 },      { "map-proj", 1, NULL, 0x27 },  { "map-res", 1, NULL, 0x28 },   { "map-lon0", 1, NULL, 0x29 },
-	{ "map-lat-ts", 1, NULL, 0x2a },
+	{ "map-lat-ts", 1, NULL, 0x2a }, { "equalise", 1, NULL, 0x2b }, { "equalise-tile", 1, NULL, 0x2c }, { "equalise-amount", 1, NULL, 0x2d },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -295,6 +300,16 @@ static int
 have_jpeg(void)
 {
 	return mdemod_jpeg_encode_host && mdemod_jpeg_free;
+}
+
+/* the equalise layer's entries (include/meteor_demod_amd_equalise.h: --equalise): weak as well */
+#pragma weak mdemod_equalise_default_opts
+#pragma weak mdemod_equalise_host
+
+static int
+have_equalise(void)
+{
+	return mdemod_equalise_default_opts && mdemod_equalise_host;
 }
 
 /* what --overlay / --graticule ask of every map and mosaic */
@@ -469,6 +484,14 @@ usage(const char *prog)
         "                           baseline JPEG <same name>.jpg of that quality (1 .. 100), encoded on the GPU, instead of the\n"
         "                           .pgm / .ppm; world files keep their names.  One line on stdout per file, and one at the end:\n"
         "                           files, bytes of pictures in, bytes of JPEG out\n"
+        "       --equalise <clip>   With --image and --rectify, --composite or --map: local contrast (CLAHE) on the GPU for every\n"
+        "                           derived picture (_rect, the composite, _map, _mosaic, _polar) in place, after it is composed\n"
+        "                           and before lines are drawn on it or it is written: per tile a histogram of the valid pixels\n"
+        "                           clipped at <clip> times a flat one (1 .. 256; 3 is usual), tables blended between tile\n"
+        "                           centres; colour pictures through their luminance.  The channel pictures stay as decoded and\n"
+        "                           no file changes its name.  One line on stdout per picture: tile, clip, tiles, empty tiles\n"
+        "       --equalise-tile <pixels>   With --equalise: the tile, a multiple of 8, 16 .. 512 (default: 128)\n"
+        "       --equalise-amount <percent>  With --equalise: how much of the equalised picture is taken, 0 .. 100 (default: 100)\n"
         "       --diff              With --cadu / --vcdu: the sender codes differentially (NRZ-M); the frame pass searches\n"
 	        "                           the differential marker and undoes the coding after the Viterbi decoder\n"
 	        "       --skew              With --cadu / --vcdu: the rails may stand one symbol apart, as after -m oqpsk when\n"
@@ -982,6 +1005,25 @@ beside(const char *s_name, const char *ext)
  * have joined. */
 static struct { unsigned quality; unsigned long long files, bytes_in, bytes_out; } jpeg_req;
 
+/* --equalise: the clip in percent (0: not given), the tile and the amount (0 .. 256) */
+static struct { unsigned clip_percent, tile, amount; int tile_given, amount_given; } equalise_req = { 0, 128, 256, 0, 0 };
+
+/* --equalise: a derived picture in place under its own mask (valid_step lines of the picture per line of the mask), before lines are
+ * drawn on a copy of it and before it is written, and its line on stdout.  Nothing without the option.  0, or the exit status. */
+static int
+equalise_picture(const char *name, uint8_t *pixels, const uint8_t *valid, uint32_t width, uint32_t height, uint32_t planes, uint32_t valid_step, int device)
+{
+	if (!equalise_req.clip_percent || !height || !width) return 0;
+	mdemod_equalise_opts eo;
+	mdemod_equalise_summary es;
+	mdemod_equalise_default_opts(&eo);
+	eo.tile = equalise_req.tile; eo.clip_percent = equalise_req.clip_percent; eo.amount = equalise_req.amount; eo.valid_step = valid_step;
+	const int rc = mdemod_equalise_host(&eo, pixels, valid, width, height, planes, &es, device);
+	if (rc != MDEMOD_OK) { fprintf(stderr, "--equalise: %s: %s\n", name, why_of(rc)); return rc == MDEMOD_ERR_PARAM ? 1 : 2; }
+	printf("%s: equalised: tile %u, clip %g, %u x %u tiles, %u empty\n", name, eo.tile, eo.clip_percent / 100.0, es.nx, es.ny, es.empty_tiles);
+	return 0;
+}
+
 /* One picture of the program, pixels[height][width][planes], into `name`, which ends in ".pgm" or ".ppm": as that binary P5 / P6
  * file, or with --jpeg encoded on the GPU into the same name ending in ".jpg" (`name` is changed), with one line on stdout that names
  * the file.  `what` is the option the messages begin with.  0, or the exit status. */
@@ -1084,7 +1126,8 @@ picture_files(const char *s_name, const mdemod_image_result *res, const struct v
 		snprintf(ext, sizeof ext, "_%u_rect.pgm", (unsigned)req->apids[k]);
 		char *name = beside(s_name, ext);
 		if (!name) { fprintf(stderr, "--rectify: could not open the picture\n"); code = 1; }
-		else code = write_picture("--rectify", name, pic.pixels, pic.width, pic.lines, 1, device);
+		else if (!(code = equalise_picture(name, pic.pixels, pic.valid, pic.width, pic.lines, 1, 8, device)))
+			code = write_picture("--rectify", name, pic.pixels, pic.width, pic.lines, 1, device);
 		free(name);
 		mdemod_picture_free(&pic);
 	}
@@ -1104,7 +1147,8 @@ picture_files(const char *s_name, const mdemod_image_result *res, const struct v
 	snprintf(ext, sizeof ext, "_%s.ppm", tag);
 	char *name = beside(s_name, ext);
 	if (!name) { fprintf(stderr, "--composite: could not open the picture\n"); code = 1; }
-	else code = write_picture("--composite", name, pic.pixels, pic.width, pic.lines, 3, device);
+	else if (!(code = equalise_picture(name, pic.pixels, pic.valid, pic.width, pic.lines, 3, 8, device)))
+		code = write_picture("--composite", name, pic.pixels, pic.width, pic.lines, 3, device);
 	if (!code)
 		printf("%s: composite %s: %u x %u%s; stretch R %u .. %u, G %u .. %u, B %u .. %u; %.1f %% of pixels valid\n", base ? base : s_name,
 		       tag, pic.width, pic.lines, req->rectify ? " rectified" : "",
@@ -1278,7 +1322,8 @@ map_file(const char *s_name, const mdemod_image_result *res, const struct vcdu_r
 	snprintf(ext, sizeof ext, "_%s_map.%s", tag, planes == 3 ? "ppm" : "pgm");
 	char *name = beside(s_name, ext), *base = beside(s_name, "");
 	if (!name) { fprintf(stderr, "--map: could not open the picture\n"); code = 1; }
-	else code = write_picture("--map", name, map.pixels, map.width, map.height, planes, device);
+	else if (!(code = equalise_picture(name, map.pixels, map.valid, map.width, map.height, planes, 1, device)))
+		code = write_picture("--map", name, map.pixels, map.width, map.height, planes, device);
 	free(name);
 	snprintf(ext, sizeof ext, "_%s_map.wld", tag);
 	name = code ? NULL : beside(s_name, ext);
@@ -1339,7 +1384,8 @@ mosaic_file(const char *base, const mdemod_mosaic_pass *passes, uint32_t n, cons
 	char *name = malloc(len);
 	if (name) snprintf(name, len, "%s_%s_mosaic.%s", base, tag, planes == 3 ? "ppm" : "pgm");
 	if (!name) { fprintf(stderr, "--mosaic: could not open the picture\n"); code = 1; }
-	else code = write_picture("--mosaic", name, mos.pixels, mos.width, mos.height, planes, device);
+	else if (!(code = equalise_picture(name, mos.pixels, mos.valid, mos.width, mos.height, planes, 1, device)))
+		code = write_picture("--mosaic", name, mos.pixels, mos.width, mos.height, planes, device);
 	if (!code) {
 		char wld[160];
 		snprintf(name, len, "%s_%s_mosaic.wld", base, tag);
@@ -1474,7 +1520,8 @@ polar_file(const char *stem, const mdemod_polar_pass *passes, uint32_t n, const 
 	if (!code && !name) { fprintf(stderr, "--map-proj stereo: out of memory\n"); code = 2; }
 	if (!code) {
 		snprintf(name, len, "%s_%s_polar.%s", stem, tag, planes == 3 ? "ppm" : "pgm");
-		code = write_picture("--map-proj stereo", name, pic.pixels, pic.frame.width, pic.frame.height, planes, device);
+		if (!(code = equalise_picture(name, pic.pixels, pic.valid, pic.frame.width, pic.frame.height, planes, 1, device)))
+			code = write_picture("--map-proj stereo", name, pic.pixels, pic.frame.width, pic.frame.height, planes, device);
 	}
 	for (int t = 0; t < 2 && !code; t++) {
 		snprintf(name, len, "%s_%s_polar.%s", stem, tag, t ? "prj" : "wld");
@@ -1839,6 +1886,32 @@ main(int argc, char **argv)
 			jpeg_req.quality = (unsigned)q;
 			break;
 		}
+		case 0x2b: {
+			char *end;
+			const double v = strtod(optarg, &end);
+			if (end == optarg || *end || !(v >= 1.0 && v <= 256.0)) { fprintf(stderr, "--equalise: a clip limit, 1 .. 256 (times a flat histogram; 3 is usual)\n"); return 1; }
+			equalise_req.clip_percent = (unsigned)(100.0 * v + 0.5);
+			break;
+		}
+		case 0x2c: {
+			char *end;
+			const long v = strtol(optarg, &end, 10);
+			if (end == optarg || *end || v < MDEMOD_EQUALISE_MIN_TILE || v > MDEMOD_EQUALISE_MAX_TILE || v % 8) {
+				fprintf(stderr, "--equalise-tile: pixels, a multiple of 8, 16 .. 512\n");
+				return 1;
+			}
+			equalise_req.tile = (unsigned)v;
+			equalise_req.tile_given = 1;
+			break;
+		}
+		case 0x2d: {
+			char *end;
+			const double v = strtod(optarg, &end);
+			if (end == optarg || *end || !(v >= 0.0 && v <= 100.0)) { fprintf(stderr, "--equalise-amount: percent, 0 .. 100\n"); return 1; }
+			equalise_req.amount = (unsigned)(2.56 * v + 0.5);
+			equalise_req.amount_given = 1;
+			break;
+		}
 		case 0x27:
 			if (!strcmp(optarg, "stereo")) vreq.polar = 1;
 			else if (!strcmp(optarg, "latlon")) vreq.polar = 0;
@@ -2015,6 +2088,22 @@ main(int argc, char **argv)
 	}
 	if (overlay_opts_given && !n_overlay) {
 		fprintf(stderr, "--overlay-colour / --overlay-width: only with --overlay (they are its options)\n");
+		return 1;
+	}
+	if ((equalise_req.tile_given || equalise_req.amount_given) && !equalise_req.clip_percent) {
+		fprintf(stderr, "--equalise-tile / --equalise-amount: only with --equalise (they are its options)\n");
+		return 1;
+	}
+	if (equalise_req.clip_percent && !want_image) {
+		fprintf(stderr, "--equalise: only with --image (it works on its pictures)\n");
+		return 1;
+	}
+	if (equalise_req.clip_percent && !(vreq.rectify || vreq.composite || map_fname)) {
+		fprintf(stderr, "--equalise: only with --rectify, --composite or --map (it works on the derived pictures; the channel pictures stay as decoded)\n");
+		return 1;
+	}
+	if (equalise_req.clip_percent && !have_equalise()) {
+		fprintf(stderr, "--equalise: this build of libmeteor_demod_amd has no equalise layer\n");
 		return 1;
 	}
 	if (jpeg_req.quality && !want_image) {

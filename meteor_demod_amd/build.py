@@ -180,7 +180,8 @@ def build(force: bool = False, verbose: bool = False) -> dict[str, Path]:
              (CSRC / "mosaic.hip", "mosaic", []), (CSRC / "mosaic_host.cpp", "mosaic_host", []),
              (CSRC / "overlay.hip", "overlay", []), (CSRC / "overlay_host.cpp", "overlay_host", []),
              (CSRC / "jpeg.hip", "jpeg", []), (CSRC / "jpeg_host.cpp", "jpeg_host", []),
-             (CSRC / "polar.hip", "polar", []), (CSRC / "polar_host.cpp", "polar_host", [])]
+             (CSRC / "polar.hip", "polar", []), (CSRC / "polar_host.cpp", "polar_host", []),
+             (CSRC / "equalise.hip", "equalise", []), (CSRC / "equalise_host.cpp", "equalise_host", [])]
     # the assembly of the rotating register window is generated (csrc/gen_rotwin_asm.py -> csrc/rotwin_asm.h)
     for gen, inc in ((CSRC / "gen_rotwin_asm.py", CSRC / "rotwin_asm.h"), (CSRC / "gen_rotpk_asm.py", CSRC / "rotpk_asm.h")):
         if force or _stale(inc, [gen]):
