@@ -52,18 +52,31 @@ typedef struct {
 	int64_t  clk_ramp64;    /* Doppler on the symbol clock: change of sym_step per sample, units of 2^-64 symbol per sample^2 */
 } synth_stream;
 
-/* (a * b) >> 32 for a < 2^63 and a signed b, exact through the 128-bit product */
-SYNTH_HD uint64_t
-synth_mul_shr32(uint64_t a, int64_t b)
+/* the 128-bit product a * b */
+SYNTH_HD void
+synth_mul128(uint64_t a, uint64_t b, uint64_t *hi, uint64_t *lo)
 {
-	const uint64_t m = b < 0 ? (uint64_t)(-b) : (uint64_t)b;
 #if defined(__HIP_DEVICE_COMPILE__)
-	const uint64_t hi = __umul64hi(a, m), lo = a * m;
+	*hi = __umul64hi(a, b);
+	*lo = a * b;
 #else
-	const unsigned __int128 pr = (unsigned __int128)a * m;
-	const uint64_t hi = (uint64_t)(pr >> 64), lo = (uint64_t)pr;
+	const unsigned __int128 pr = (unsigned __int128)a * b;
+	*hi = (uint64_t)(pr >> 64);
+	*lo = (uint64_t)pr;
 #endif
-	const uint64_t r = (hi << 32) | (lo >> 32);
+}
+
+/* (n(n-1)/2 * |b|) >> 32 modulo 2^64 with the sign of b, exact for every 64-bit n: the triangle (up to 127 bits) stays the
+ * 128-bit product of its two factors, and of its product with |b| (up to 190 bits) only bits 32..95 are kept */
+SYNTH_HD uint64_t
+synth_tri_mul_shr32(uint64_t n, int64_t b)
+{
+	const uint64_t m = b < 0 ? (uint64_t)0 - (uint64_t)b : (uint64_t)b;
+	uint64_t thi, tlo, hi, lo;
+	if (n & 1) synth_mul128(n, (n - 1) >> 1, &thi, &tlo);
+	else synth_mul128(n >> 1, n - 1, &thi, &tlo);
+	synth_mul128(tlo, m, &hi, &lo);
+	const uint64_t r = ((hi << 32) | (lo >> 32)) + ((thi * m) << 32);
 	return b < 0 ? (uint64_t)0 - r : r;
 }
 
@@ -131,8 +144,8 @@ synth_noise(uint64_t seed, uint64_t n, uint64_t salt)
 SYNTH_HD void
 synth_sample(const synth_tables *tb, const synth_stream *st, uint64_t n, double *oi, double *oq)
 {
-	const uint64_t tri = (n & 1) ? n * ((n - 1) >> 1) : (n >> 1) * (n - 1);       /* n(n-1)/2 */
-	const uint64_t t = st->sym_phase0 + n * st->sym_step + (st->clk_ramp64 ? synth_mul_shr32(tri, st->clk_ramp64) : 0);
+	const uint64_t tri = (n & 1) ? n * ((n - 1) >> 1) : (n >> 1) * (n - 1);       /* n(n-1)/2 modulo 2^64 */
+	const uint64_t t = st->sym_phase0 + n * st->sym_step + (st->clk_ramp64 ? synth_tri_mul_shr32(n, st->clk_ramp64) : 0);
 	const double bi = synth_rail(tb, st->seed, t, 0);
 	const double bq = synth_rail(tb, st->seed, st->oqpsk ? t - 0x80000000ull : t, 1);
 

@@ -12,7 +12,8 @@ test_every_compiled_instance_has_exactly_one_row until it has a row here.
 The signal of a row is the `c1_fade` pattern of tests/golden_cases.py on the row's configuration: signal at Es/N0 = 20 dB, noise
 only (rms 1.0, Es/N0 = -30 dB), signal again - five streams that differ in seed, carrier offset, clock error and segment lengths.
 The GPU does not run the lead-in: the oracle does, and its loop state and filter history go into the context through
-mdemod_set_state / mdemod_set_history right before a window of +-WINDOW symbols around a transition."""
+mdemod_set_state / mdemod_set_history right before a window of +-WINDOW symbols around a transition.  That the device generator
+gives the host generator's samples at n0 != 0 is held by tests/test_gpu_synth.py::test_device_equals_host_bit_for_bit."""
 from __future__ import annotations
 
 import ctypes as C
