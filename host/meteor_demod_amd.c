@@ -74,6 +74,10 @@
  * (include/meteor_demod_amd_equalise.h: CLAHE under the picture's own mask) in place, after it is composed and before lines are drawn on
  * its copy or it is written; --equalise-tile <pixels>, --equalise-amount <percent>; one line per picture.  The channel pictures stay as
  * decoded.  Only with --image and --rectify, --composite or --map.  Weak references.
+ * --sun takes the cosine of the sun's zenith angle out of the reflective channels (APIDs 64 .. 66) of the swath pictures on the GPU
+ * (include/meteor_demod_amd_sun.h), after the channel pictures are written - they stay as decoded - and before any derived picture or
+ * the mosaic is made of them; --sun-ref <deg>, --sun-limit <deg>; one line per file.  Only with --image and --map <tle file>: the orbit
+ * comes from the element set.  Weak references.
  * Known deviation: if the final flush would read past the 1024-byte ring (ring_idx >
  * 512, where the reference reads out of bounds) only the bytes inside the ring are
  * written.
@@ -104,6 +108,7 @@
 #include "meteor_demod_amd_overlay.h"
 #include "meteor_demod_amd_jpeg.h"
 #include "meteor_demod_amd_equalise.h"
+#include "meteor_demod_amd_sun.h"
 #ifdef MDEMOD_TUI
 #include "tui.h"
 #endif
@@ -144,6 +149,7 @@ static const struct option longopts[] = {
 	{ "overlay", 1, NULL, 0x22 },   { "graticule", 1, NULL, 0x23 }, { "overlay-colour", 1, NULL, 0x24 }, { "overlay-width", 1, NULL, 0x25 },
 	{ "jpeg", 1, NULL, 0x26 },      { "map-proj", 1, NULL, 0x27 },  { "map-res", 1, NULL, 0x28 },   { "map-lon0", 1, NULL, 0x29 },
 	{ "map-lat-ts", 1, NULL, 0x2a }, { "equalise", 1, NULL, 0x2b }, { "equalise-tile", 1, NULL, 0x2c }, { "equalise-amount", 1, NULL, 0x2d },
+	{ "sun", 0, NULL, 0x2e },       { "sun-ref", 1, NULL, 0x2f },   { "sun-limit", 1, NULL, 0x30 },
 	{ NULL, 0, NULL, 0 }
 };
 
@@ -310,6 +316,15 @@ static int
 have_equalise(void)
 {
 	return mdemod_equalise_default_opts && mdemod_equalise_host;
+}
+
+/* the sun layer's entries (include/meteor_demod_amd_sun.h: --sun): weak as well */
+#pragma weak mdemod_sun_default_opts
+#pragma weak mdemod_sun_correct_host
+static int
+have_sun(void)
+{
+	return mdemod_sun_default_opts && mdemod_sun_correct_host;
 }
 
 /* what --overlay / --graticule ask of every map and mosaic */
@@ -492,6 +507,11 @@ usage(const char *prog)
         "                           no file changes its name.  One line on stdout per picture: tile, clip, tiles, empty tiles\n"
         "       --equalise-tile <pixels>   With --equalise: the tile, a multiple of 8, 16 .. 512 (default: 128)\n"
         "       --equalise-amount <percent>  With --equalise: how much of the equalised picture is taken, 0 .. 100 (default: 100)\n"
+        "       --sun               With --image and --map: take the cosine of the sun's zenith angle out of the reflective channels\n"
+        "                           (APIDs 64 .. 66) on the GPU before any derived picture or the mosaic is made; the channel\n"
+        "                           pictures stay as decoded\n"
+        "       --sun-ref <deg>     With --sun: the zenith angle whose counts stay as they are, 0 .. 80 (default: 45)\n"
+        "       --sun-limit <deg>   With --sun: the zenith angle beyond which the gain grows no further, 60 .. 89 (default: 85)\n"
         "       --diff              With --cadu / --vcdu: the sender codes differentially (NRZ-M); the frame pass searches\n"
 	        "                           the differential marker and undoes the coding after the Viterbi decoder\n"
 	        "       --skew              With --cadu / --vcdu: the rails may stand one symbol apart, as after -m oqpsk when\n"
@@ -1567,6 +1587,47 @@ polar_files(const char *stem, const mdemod_image_result *const *results, int n_r
 	return code;
 }
 
+/* --sun: given, and the two angles (0: the library's default) */
+static struct { int on; double ref_deg, limit_deg; int ref_given, limit_given; } sun_req;
+
+/* --sun: the reflective channels of one file's pictures in place, with the options of --map, and the file's line on stdout.  Nothing
+ * without the option or without a picture.  0, or the exit status. */
+static int
+sun_pictures(const char *s_name, mdemod_image_result *res, const struct vcdu_req *req, int device)
+{
+	if (!sun_req.on || !res->summary.rows) return 0;
+	mdemod_sun_opts so;
+	mdemod_sun_summary ss;
+	mdemod_map_opts mo;
+	mdemod_sun_default_opts(&so);
+	if (sun_req.ref_given) so.ref_deg = sun_req.ref_deg;
+	if (sun_req.limit_given) so.limit_deg = sun_req.limit_deg;
+	map_options(req, &mo);
+	/* (the sun layer's header repeats the map layer's options and element set field for field) */
+	mdemod_sun_pass_opts po;
+	mdemod_sun_orbit orbit;
+	_Static_assert(sizeof po == sizeof mo && sizeof orbit == sizeof req->tle, "the sun layer's pass is the map layer's");
+	memcpy(&po, &mo, sizeof po);
+	memcpy(&orbit, &req->tle, sizeof orbit);
+	uint8_t *image[3] = { res->image[0], res->image[1], res->image[2] };
+	const int rc = mdemod_sun_correct_host(&so, &po, &orbit, image, req->apids, res->summary.rows, res->place, res->sinfo, res->n_packets, &ss, device);
+	if (rc != MDEMOD_OK) { fprintf(stderr, "--sun: %s: %s\n", s_name, why_of(rc)); return rc == MDEMOD_ERR_PARAM ? 1 : 2; }
+	char *base = beside(s_name, "");
+	char slots[32] = "";
+	unsigned long long sat = 0, pixels = 0;
+	for (int k = 0; k < 3; k++) {
+		if (!(ss.slot_mask >> k & 1u)) continue;
+		snprintf(slots + strlen(slots), sizeof slots - strlen(slots), "%s%u", *slots ? ", " : "", (unsigned)req->apids[k]);
+		sat += ss.saturated[k];
+		pixels += (unsigned long long)res->summary.rows * 8 * MDEMOD_IMAGE_WIDTH;
+	}
+	printf("%s: sun: zenith %.2f .. %.2f deg, reference %g, limit %g (%u of %u nodes beyond it, %u missing); corrected: %s; %.3f %% of pixels saturated\n",
+	       base ? base : s_name, ss.zenith_min, ss.zenith_max, so.ref_deg, so.limit_deg, ss.at_limit, ss.nodes, ss.missing, *slots ? slots : "none",
+	       pixels ? 100.0 * (double)sat / (double)pixels : 0.0);
+	free(base);
+	return 0;
+}
+
 /* --image: n VCDUs through the image layer, one PGM per active channel that received a strip beside the output file, one line.
  * 0, or the exit status. */
 static int
@@ -1600,6 +1661,7 @@ image_files(const char *s_name, const uint8_t *vcdu, const mdemod_rs_info *info,
 		       rows ? 100.0 * (double)res.summary.cells_filled / (3.0 * rows * MDEMOD_IMAGE_CELLS) : 0.0);
 		free(base);
 	}
+	if (!code) code = sun_pictures(s_name, &res, req, device);                  /* (--sun: everything below comes from the corrected buffers) */
 	if (!code && (req->rectify || req->composite)) code = picture_files(s_name, &res, req, device);
 	if (!code && req->map && req->polar) {
 		const mdemod_image_result *one[1] = { &res };
@@ -1912,6 +1974,25 @@ main(int argc, char **argv)
 			equalise_req.amount_given = 1;
 			break;
 		}
+		case 0x2e:
+			sun_req.on = 1;
+			break;
+		case 0x2f: {
+			char *end;
+			const double v = strtod(optarg, &end);
+			if (end == optarg || *end || !(v >= 0.0 && v <= MDEMOD_SUN_MAX_REF)) { fprintf(stderr, "--sun-ref: degrees of zenith angle, 0 .. 80\n"); return 1; }
+			sun_req.ref_deg = v;
+			sun_req.ref_given = 1;
+			break;
+		}
+		case 0x30: {
+			char *end;
+			const double v = strtod(optarg, &end);
+			if (end == optarg || *end || !(v >= MDEMOD_SUN_MIN_LIMIT && v <= MDEMOD_SUN_MAX_LIMIT)) { fprintf(stderr, "--sun-limit: degrees of zenith angle, 60 .. 89\n"); return 1; }
+			sun_req.limit_deg = v;
+			sun_req.limit_given = 1;
+			break;
+		}
 		case 0x27:
 			if (!strcmp(optarg, "stereo")) vreq.polar = 1;
 			else if (!strcmp(optarg, "latlon")) vreq.polar = 0;
@@ -2100,6 +2181,22 @@ main(int argc, char **argv)
 	}
 	if (equalise_req.clip_percent && !(vreq.rectify || vreq.composite || map_fname)) {
 		fprintf(stderr, "--equalise: only with --rectify, --composite or --map (it works on the derived pictures; the channel pictures stay as decoded)\n");
+		return 1;
+	}
+	if ((sun_req.ref_given || sun_req.limit_given) && !sun_req.on) {
+		fprintf(stderr, "--sun-ref / --sun-limit: only with --sun (they are its options)\n");
+		return 1;
+	}
+	if (sun_req.on && !want_image) {
+		fprintf(stderr, "--sun: only with --image (it works on its pictures)\n");
+		return 1;
+	}
+	if (sun_req.on && !map_fname) {
+		fprintf(stderr, "--sun: only with --map <tle file> (the sun's angle needs the orbit and the line times; the channel pictures stay as decoded)\n");
+		return 1;
+	}
+	if (sun_req.on && !have_sun()) {
+		fprintf(stderr, "--sun: this build of libmeteor_demod_amd has no sun layer\n");
 		return 1;
 	}
 	if (equalise_req.clip_percent && !have_equalise()) {

@@ -181,7 +181,8 @@ def build(force: bool = False, verbose: bool = False) -> dict[str, Path]:
              (CSRC / "overlay.hip", "overlay", []), (CSRC / "overlay_host.cpp", "overlay_host", []),
              (CSRC / "jpeg.hip", "jpeg", []), (CSRC / "jpeg_host.cpp", "jpeg_host", []),
              (CSRC / "polar.hip", "polar", []), (CSRC / "polar_host.cpp", "polar_host", []),
-             (CSRC / "equalise.hip", "equalise", []), (CSRC / "equalise_host.cpp", "equalise_host", [])]
+             (CSRC / "equalise.hip", "equalise", []), (CSRC / "equalise_host.cpp", "equalise_host", []),
+             (CSRC / "sun.hip", "sun", []), (CSRC / "sun_host.cpp", "sun_host", [])]
     # the assembly of the rotating register window is generated (csrc/gen_rotwin_asm.py -> csrc/rotwin_asm.h)
     for gen, inc in ((CSRC / "gen_rotwin_asm.py", CSRC / "rotwin_asm.h"), (CSRC / "gen_rotpk_asm.py", CSRC / "rotpk_asm.h")):
         if force or _stale(inc, [gen]):
