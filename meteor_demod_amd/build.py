@@ -240,7 +240,8 @@ def build(force: bool = False, verbose: bool = False) -> dict[str, Path]:
     if host_src.exists():
         exe = LIB / "meteor_demod_amd"
         tui_src = [ROOT / "host" / "tui.c", ROOT / "host" / "tui.h"]
-        if force or _stale(exe, [host_src, *sorted((ROOT / "include").glob("*.h")), so, *tui_src]):
+        parts = [ROOT / "host" / "cli_opts.h", ROOT / "host" / "cli_products.h"]      # (included by host_src)
+        if force or _stale(exe, [host_src, *parts, *sorted((ROOT / "include").glob("*.h")), so, *tui_src]):
             cc = shutil.which("gcc") or shutil.which("cc")
             # the full-screen display needs ncurses (as the reference's ENABLE_TUI does); linked statically so that the binary
             # that travels to another box of this image needs nothing beyond libc there

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Transcripts of what the C host says and writes for its map, mosaic and polar products: tests/golden/cli_products/<case>.*.
+"""Transcripts of what the C host says and writes for its picture, map, mosaic and polar products: tests/golden/cli_products/<case>.*.
 
     python tests/golden/make_cli_products.py <path of a meteor_demod_amd binary> [device]
 
@@ -32,7 +32,13 @@ CASES = {
     "stereo_per_channel_jpeg": (("one.wav",), (*_STEREO, "--jpeg", "85")),
     "mosaic_one_file_without_picture": (("one.wav", "noise.wav"), (*_MAP, "--map-scale", "60", "--composite", "321", "--mosaic", "both")),
     "stereo_mosaic_one_file_without_picture": (("one.wav", "noise.wav"), (*_STEREO, "--composite", "321", "--mosaic", "both")),
+    "rectify_321_equalise": (("one.wav",), ("--image", "--rectify", "--composite", "321", "--equalise", "3", "--equalise-tile", "64")),
+    "map_vcdu_sun": (("one.wav",), (*_MAP, "--vcdu", "--map-scale", "60", "--sun", "--sun-ref", "50")),
+    "map_overlay_jpeg": (("one.wav",), (*_MAP, "--map-scale", "60", "--overlay", "coast.txt", "--overlay-colour", "00ff00", "--overlay-width", "2", "--jpeg", "85")),
+    "mosaic_321_jpeg": (("one.wav", "two.wav"), (*_MAP, "--map-scale", "60", "--composite", "321", "--mosaic", "both", "--jpeg", "85")),
 }
+# the file of --overlay: two short polylines inside the grid of map_per_channel (lat 12.7 .. 16.5, lon 116.4 .. 140.6)
+COAST = "120 13\n128 15\n136 16\n>\n125 16\n130 13.5\n"
 
 
 def transcript(exe, case: str, workdir: Path, device: int = 0) -> dict:
@@ -42,6 +48,7 @@ def transcript(exe, case: str, workdir: Path, device: int = 0) -> dict:
     files, flags = CASES[case]
     _, iq = MU.recording()
     (workdir / "tle.txt").write_text((HERE / "map_tle.txt").read_text())
+    (workdir / "coast.txt").write_text(COAST)
     for name in files:
         (workdir / name).write_bytes(U.wav_bytes(U.REC_SAMPLERATE, U.noise(len(iq), 5) if "noise" in name else iq))
     given = {p.name for p in workdir.iterdir()}
