@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pll_flags.h"
+
 #pragma clang fp contract(off)
 
 #define MD_TWO_PI_D 6.283185307179586476925286766559   /* 2*M_PI  (pll.c:61,113; timing.c:80) */
@@ -27,6 +29,26 @@ struct cf32 { float re, im; };
  * comparison is the comparison's own mask.  Same semantics: over the active lanes. */
 __device__ __forceinline__ bool md_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 __device__ __forceinline__ bool md_all(bool p) { return __builtin_amdgcn_ballot_w64(!p) == 0ull; }
+
+/* Per lane: the lane's bit of `mask` set ? b : a, for a mask that was put together on the scalar unit (a bool made of several
+ * comparisons goes back through the vector unit when it is voted on, see above; a 64-bit scalar cannot be a select's condition in
+ * C++).  One v_cndmask_b32 with the mask in an SGPR pair. */
+template <typename T>
+__device__ __forceinline__ T md_lane_select(uint64_t mask, T a, T b)
+{
+	static_assert(sizeof(T) == 4, "one 32-bit register");
+	T r;
+	asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(mask));
+	return r;
+}
+
+/* ... and the lane's bit itself, 0 or 1 */
+__device__ __forceinline__ uint32_t md_lane_bit(uint64_t mask)
+{
+	uint32_t r;
+	asm("v_cndmask_b32 %0, 0, 1, %1" : "=v"(r) : "s"(mask));
+	return r;
+}
 
 /* MAX(-b, MIN(b, x)) of the reference's macros (utils.h: `(a) < (b) ? (a) : (b)`) for a bound b > 0, as ONE v_med3_f32 instead of
  * two comparisons and two selects (each of the four a 4.4-cycle VALU instruction on gfx950: tools/ubench/valu_mix.hip).  Equal for
@@ -353,9 +375,17 @@ md_pll_update(PllState &p, const float *lut, float alpha, float beta, float fmax
 /* pll.c:100-130 with the three flags kept PACKED in one word (bit 0 locked, bit 1 locked_once, bit 2 updown > 0: the layout of
  * the state array), the lock detector as bit arithmetic: v_and / v_or / v_xor / v_add are 2.6-cycle instructions on gfx950, the
  * compare + select pairs md_pll_update's int fields compile to 4.4 each (and there were nine of each per firing).  Same values,
- * same order of the float and double operations.  Returns nonzero when `locked` changed; first != 0: the first lock ever. */
+ * same order of the float and double operations.  Returns nonzero when `locked` changed; first != 0: the first lock ever.
+ *
+ * EARLY_OUT (the rotating-window bodies): the flag arithmetic and the turn-round change something only on a symbol where a lane
+ * locks, unlocks or stands at +-fmax - a handful of symbols in a stream's life, one in 2 * fmax / 1e-6 for a sweeping one - and
+ * return fl, first = 0, 0 on every other.  The conditions are taken as lane masks (v_cmp straight into the mask, combined on the
+ * scalar unit) and ONE wave vote decides: no lane with an event, no integer arithmetic; any lane, and the whole wave runs
+ * pll_flags_step (pll_flags.h: the arithmetic below, the identity for the lanes without an event).  The sweep asks the mask
+ * `locked after this symbol` (pll_flags_locked_after) where it asked the new flag word.  A NaN in err or freq is no event on either
+ * path: every comparison is false.  The float and double operations and their order are the same with and without. */
 struct PllWord { float phase, freq, err; };
-template <bool UNIFORM = false>
+template <bool UNIFORM = false, bool EARLY_OUT = false>
 __device__ __forceinline__ uint32_t
 md_pll_update_packed(PllWord &p, uint32_t &fl, const float *lut, float alpha, float beta, float fmax, float i, float q, uint32_t &first)
 {
@@ -370,6 +400,26 @@ md_pll_update_packed(PllWord &p, uint32_t &fl, const float *lut, float alpha, fl
 
 	const float decayed = p.err * (1.0f - 0.001f);
 	p.err = (float)((double)decayed + fabs((double)e) * (double)0.001f);    /* pll.c:117 */
+
+	if constexpr (EARLY_OUT) {
+		/* the conditions as lane masks: a ballot of a comparison is the comparison's own mask, over the active lanes */
+		const uint64_t m_below = __builtin_amdgcn_ballot_w64(p.err < 85.0f), m_above = __builtin_amdgcn_ballot_w64(p.err > 105.0f);
+		const uint64_t m_locked = __builtin_amdgcn_ballot_w64((fl & 1u) != 0);
+		const uint64_t m_lock_event = (m_below & ~m_locked) | (m_above & m_locked);
+		/* pll.c:125 with `locked` as pll.c:117-123 leave it: the old one unless this symbol is a lock event */
+		const float swept = (float)((double)p.freq + ((fl & 4u) ? 0.000001 : -0.000001));
+		p.freq = md_lane_select(m_locked ^ m_lock_event, swept, p.freq);
+		const uint64_t m_turn = __builtin_amdgcn_ballot_w64(fabsf(p.freq) >= fmax);     /* pll.c:126-127 have something to do */
+		first = 0;
+		uint32_t changed = 0;
+		if (__builtin_expect((m_lock_event | m_turn) != 0ull, 0)) {
+			const PllFlagStep s = pll_flags_step(fl, md_lane_bit(m_below), md_lane_bit(m_above),
+			                                     p.freq >= fmax ? PLL_FREQ_HIGH : (p.freq <= -fmax ? PLL_FREQ_LOW : PLL_FREQ_INSIDE));
+			fl = s.fl; first = s.first; changed = s.changed;
+		}
+		p.freq = md_clamp_sym(p.freq, fmax);                                /* MAX(-fmax, MIN(fmax, freq)) */
+		return changed;
+	}
 
 	/* pll.c:117-123: lock below 85, unlock above 105 (the two exclude each other) */
 	const uint32_t below = (p.err < 85.0f) ? 1u : 0u, above = (p.err > 105.0f) ? 1u : 0u;

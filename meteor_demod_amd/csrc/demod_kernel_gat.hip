@@ -45,6 +45,7 @@ struct WinG {
 	static constexpr int G = GFmt<FMT>::G, kTaps = KT, kBack = KT - 1, AMAX = G - 1, NS = KT + AMAX, NW = 4 * ((NS + 3) / 4), SLIDE = 4, MAXSL = 1, DEPTH = 1,
 	                     BLOCK = MDEMOD_RW_BLOCK, ROTN = 1, RING = 32, REGSLOTS = 0;
 	static constexpr bool GATHER = true, SCALAR_SLIDE = false, VCONST = false;
+	static constexpr bool LOCK_EARLY_OUT = true;        /* the lock detector's flag arithmetic behind one wave vote (demod_device.h: md_pll_update_packed) */
 	static_assert(NS % G == 0 && NS / G <= 36, "whole 16-byte loads, and few enough of them to stay in registers");
 	typedef typename RFmt<FMT>::sample_t sample_t;
 	__device__ __forceinline__ void setup(uint32_t) {}

@@ -12,7 +12,8 @@
  *     slide(granules, rot, base)       (SCALAR_SLIDE policies) put(granules, rot), then rot and base move on by one slide, as scalars
  *     fir(ctab_addr, a, bank, C, rot, re, im)      filter.c:46-65 for a lane whose taps start `a` slots into the window
  * and the geometry (kTaps, kBack, NW, SLIDE, AMAX, MAXSL, BLOCK, ROTN: rotations before the window is where it started,
- * RING: symbols of the per-lane output ring).  Everything else - symbol clock, AGC, NCO, loops, lock
+ * RING: symbols of the per-lane output ring; LOCK_EARLY_OUT: the lock detector's flag arithmetic behind one wave vote,
+ * md_pll_update_packed in demod_device.h).  Everything else - symbol clock, AGC, NCO, loops, lock
  * detector, output ring, state and history hand-over - is here, compiled for the registers the policy leaves to hipcc.
  */
 #ifndef MDEMOD_ROTWIN_BODY_H
@@ -438,7 +439,7 @@ rotwin_demod(const DemodLaunch &L)
 #endif
 			if (emit) {
 				uint32_t first = 0;
-				const uint32_t changed = md_pll_update_packed(pll, fl, lut, k_pll_alpha, k_pll_beta, C.pll_fmax, out_re, out_im, first);
+				const uint32_t changed = md_pll_update_packed<false, W::LOCK_EARLY_OUT>(pll,fl, lut, k_pll_alpha, k_pll_beta, C.pll_fmax, out_re, out_im, first);
 				if (__builtin_expect(changed != 0, 0)) {          /* a plain divergent branch: skipped when no lane of the wave takes it */
 					if (first) sli[S_FIRSTLOCK * 64] = (int)sym_call;
 					const int ev_call = sli[S_EVCALL * 64];
