@@ -180,6 +180,7 @@ def build(force: bool = False, verbose: bool = False) -> dict[str, Path]:
              (CSRC / "mosaic.hip", "mosaic", []), (CSRC / "mosaic_host.cpp", "mosaic_host", []),
              (CSRC / "overlay.hip", "overlay", []), (CSRC / "overlay_host.cpp", "overlay_host", []),
              (CSRC / "jpeg.hip", "jpeg", []), (CSRC / "jpeg_host.cpp", "jpeg_host", []),
+             (CSRC / "png.hip", "png", []), (CSRC / "png_host.cpp", "png_host", []),
              (CSRC / "polar.hip", "polar", []), (CSRC / "polar_host.cpp", "polar_host", []),
              (CSRC / "equalise.hip", "equalise", []), (CSRC / "equalise_host.cpp", "equalise_host", []),
              (CSRC / "sun.hip", "sun", []), (CSRC / "sun_host.cpp", "sun_host", [])]
