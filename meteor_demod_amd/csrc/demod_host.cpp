@@ -116,7 +116,6 @@ mdemod_clock_table(int32_t interp, int32_t k_safe, int32_t *out, uint32_t cap_en
 int
 mdemod_host_derive(const mdemod_params &p, HostTables &out, int generation)
 {
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
 	if (p.interp_factor < 1 || p.interp_factor > 64) REFUSE("-O %d: the interpolation factor must be 1..64", p.interp_factor);
 	if (p.rrc_order < 1 || p.rrc_order > 256) REFUSE("-f %d: the RRC order must be 1..256", p.rrc_order);
 	if (p.samplerate <= 0 || p.symrate <= 0) REFUSE("sample rate %d and symbol rate %d must be positive", p.samplerate, p.symrate);

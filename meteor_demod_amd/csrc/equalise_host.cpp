@@ -7,19 +7,13 @@
 #include <cstring>
 #include <vector>
 
+#include "buffers.h"
 #include "equalise_host.h"
 #include "mdemod_internal_api.h"
 
-#define REFUSE(...) do { if (who) mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
+#define REFUSE_IF_NAMED(...) do { if (who) mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
 
 namespace {
-
-bool
-intersect(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-	return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
 
 bool
 counted(const EqPlan &p, const uint8_t *valid, uint32_t y, uint32_t x)
@@ -43,16 +37,16 @@ eq_check(const char *who, uint32_t width, uint32_t height, uint32_t planes, cons
 	mdemod_equalise_opts o;
 	if (opts) o = *opts;
 	else mdemod_equalise_default_opts(&o);
-	if (planes != 1 && planes != 3) REFUSE("%s: planes must be 1 or 3, not %u", who, planes);
-	if (width < 1 || width > MDEMOD_EQUALISE_MAX_WIDTH) REFUSE("%s: width %u is outside 1 .. %d", who, width, MDEMOD_EQUALISE_MAX_WIDTH);
-	if (height < 1 || height > MDEMOD_EQUALISE_MAX_HEIGHT) REFUSE("%s: height %u is outside 1 .. %d", who, height, MDEMOD_EQUALISE_MAX_HEIGHT);
+	if (planes != 1 && planes != 3) REFUSE_IF_NAMED("%s: planes must be 1 or 3, not %u", who, planes);
+	if (width < 1 || width > MDEMOD_EQUALISE_MAX_WIDTH) REFUSE_IF_NAMED("%s: width %u is outside 1 .. %d", who, width, MDEMOD_EQUALISE_MAX_WIDTH);
+	if (height < 1 || height > MDEMOD_EQUALISE_MAX_HEIGHT) REFUSE_IF_NAMED("%s: height %u is outside 1 .. %d", who, height, MDEMOD_EQUALISE_MAX_HEIGHT);
 	if (o.tile < MDEMOD_EQUALISE_MIN_TILE || o.tile > MDEMOD_EQUALISE_MAX_TILE || o.tile % 8)
-		REFUSE("%s: tile %u is no multiple of 8 in %d .. %d", who, o.tile, MDEMOD_EQUALISE_MIN_TILE, MDEMOD_EQUALISE_MAX_TILE);
+		REFUSE_IF_NAMED("%s: tile %u is no multiple of 8 in %d .. %d", who, o.tile, MDEMOD_EQUALISE_MIN_TILE, MDEMOD_EQUALISE_MAX_TILE);
 	if (o.clip_percent < MDEMOD_EQUALISE_MIN_CLIP || o.clip_percent > MDEMOD_EQUALISE_MAX_CLIP)
-		REFUSE("%s: clip_percent %u is outside %d .. %d", who, o.clip_percent, MDEMOD_EQUALISE_MIN_CLIP, MDEMOD_EQUALISE_MAX_CLIP);
-	if (o.amount > MDEMOD_EQUALISE_MAX_AMOUNT) REFUSE("%s: amount %u is outside 0 .. %d", who, o.amount, MDEMOD_EQUALISE_MAX_AMOUNT);
-	if (planes == 3 && o.mode > 1) REFUSE("%s: mode %u is neither 0 (planes) nor 1 (luminance)", who, o.mode);
-	if (o.valid_step != 1 && o.valid_step != 8) REFUSE("%s: valid_step must be 1 or 8, not %u", who, o.valid_step);
+		REFUSE_IF_NAMED("%s: clip_percent %u is outside %d .. %d", who, o.clip_percent, MDEMOD_EQUALISE_MIN_CLIP, MDEMOD_EQUALISE_MAX_CLIP);
+	if (o.amount > MDEMOD_EQUALISE_MAX_AMOUNT) REFUSE_IF_NAMED("%s: amount %u is outside 0 .. %d", who, o.amount, MDEMOD_EQUALISE_MAX_AMOUNT);
+	if (planes == 3 && o.mode > 1) REFUSE_IF_NAMED("%s: mode %u is neither 0 (planes) nor 1 (luminance)", who, o.mode);
+	if (o.valid_step != 1 && o.valid_step != 8) REFUSE_IF_NAMED("%s: valid_step must be 1 or 8, not %u", who, o.valid_step);
 	plan->width = width; plan->height = height; plan->planes = planes;
 	plan->luma = planes == 3 && o.mode == MDEMOD_EQUALISE_LUMA;
 	plan->channels = planes == 3 && !plan->luma ? 3 : 1;
@@ -66,15 +60,15 @@ eq_check_buffers(const char *who, const EqPlan &p, const void *picture, const vo
 {
 	const uint64_t area = static_cast<uint64_t>(p.width) * p.height * p.planes, need = eq_public_bytes(p);
 	const uint64_t mask = static_cast<uint64_t>((p.height + p.valid_step - 1) / p.valid_step) * p.width;
-	if (!picture) REFUSE("%s: the picture is needed", who);
-	if (!work) REFUSE("%s: the workspace is needed", who);
-	if (has_out && !out) REFUSE("%s: the output is needed", who);
-	if (work_bytes < need) REFUSE("%s: the workspace needs %llu bytes, not %llu", who, static_cast<unsigned long long>(need), static_cast<unsigned long long>(work_bytes));
+	if (!picture) REFUSE_IF_NAMED("%s: the picture is needed", who);
+	if (!work) REFUSE_IF_NAMED("%s: the workspace is needed", who);
+	if (has_out && !out) REFUSE_IF_NAMED("%s: the output is needed", who);
+	if (work_bytes < need) REFUSE_IF_NAMED("%s: the workspace needs %llu bytes, not %llu", who, static_cast<unsigned long long>(need), static_cast<unsigned long long>(work_bytes));
 	if ((reinterpret_cast<uintptr_t>(picture) & 3u) || (reinterpret_cast<uintptr_t>(work) & 3u) || (has_out && (reinterpret_cast<uintptr_t>(out) & 3u)))
-		REFUSE("%s: the picture, the workspace and the output must stand at multiples of 4 bytes", who);
-	bool hit = intersect(picture, area, work, work_bytes) || intersect(valid, mask, work, work_bytes) || intersect(picture, area, valid, mask);
-	if (has_out) hit = hit || intersect(out, area, work, work_bytes) || intersect(out, area, valid, mask) || (out != picture && intersect(out, area, picture, area));
-	if (hit) REFUSE("%s: the picture, the mask, the workspace and the output intersect (only the output may be the picture itself)", who);
+		REFUSE_IF_NAMED("%s: the picture, the workspace and the output must stand at multiples of 4 bytes", who);
+	bool hit = mdm_ranges_intersect(picture, area, work, work_bytes) || mdm_ranges_intersect(valid, mask, work, work_bytes) || mdm_ranges_intersect(picture, area, valid, mask);
+	if (has_out) hit = hit || mdm_ranges_intersect(out, area, work, work_bytes) || mdm_ranges_intersect(out, area, valid, mask) || (out != picture && mdm_ranges_intersect(out, area, picture, area));
+	if (hit) REFUSE_IF_NAMED("%s: the picture, the mask, the workspace and the output intersect (only the output may be the picture itself)", who);
 	return MDEMOD_OK;
 }
 

@@ -402,8 +402,6 @@ fr_errors(const int8_t *soft, const FrvFrame *frames, const uint8_t *cadu, uint3
 
 namespace {
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 /* the weight words of the candidates kernels: bytes (I_k, Q_k, I_k+1, Q_k+1) against the pattern (the differential one for `diff`),
  * one row per h = 0, 1, 4, 5 */
 FrcWeights

@@ -11,8 +11,6 @@
 #include "frames_host.h"
 #include "mdemod_internal_api.h"
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 namespace {
 
 inline uint32_t

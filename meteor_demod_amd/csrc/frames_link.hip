@@ -6,8 +6,6 @@
 #include "frames_device.h"
 #include "hip_host.h"
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 extern "C" {
 
 int

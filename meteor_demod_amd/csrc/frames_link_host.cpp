@@ -9,8 +9,6 @@
 #include "frames_host.h"
 #include "mdemod_internal_api.h"
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 extern "C" {
 
 uint64_t

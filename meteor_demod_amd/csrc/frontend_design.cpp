@@ -47,7 +47,6 @@ mdemod_fe_phase_step(double offset_hz, int32_t samplerate)
 int
 mdemod_fe_design_host(const mdemod_params &in, const mdemod_fe_params &fe, FeDesign &out)
 {
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
 	const int32_t d = fe.decimation;
 	const int32_t tpp = fe.taps_per_phase == 0 ? MDEMOD_FE_DEFAULT_TAPS_PER_PHASE : fe.taps_per_phase;
 	if (d < 1 || d > MDEMOD_FE_MAX_DECIMATION) REFUSE("front end: decimation %d must be 1..%d", d, MDEMOD_FE_MAX_DECIMATION);
@@ -70,7 +69,6 @@ mdemod_fe_design_host(const mdemod_params &in, const mdemod_fe_params &fe, FeDes
 			REFUSE("front end: offset %.1f Hz of stream %u is not inside +-fs/2 = +-%.1f Hz", off, s, 0.5 * in.samplerate);
 		out.steps[s] = mdemod_fe_phase_step(off, in.samplerate);
 	}
-#undef REFUSE
 	out.decimation = d;
 	out.taps_per_phase = tpp;
 	out.samplerate_out = fs_out;

@@ -1,7 +1,7 @@
 /*
  * hip_host.h — what the host side of the library does with the HIP runtime, once: the error macro, the device selection, the
- * overlap check of an entry's buffers, the owner of device allocations, the launch with dynamic LDS, the private stream.  C++, for the units hipcc compiles only (the
- * host-only units that the sanitizer builds compile with g++ do not see it).
+ * owner of device allocations, the launch with dynamic LDS, the private stream; the overlap check of an entry's buffers comes with it
+ * (buffers.h).  C++, for the units hipcc compiles only (the host-only units that the sanitizer builds compile with g++ do not see it).
  */
 #ifndef MDEMOD_HIP_HOST_H
 #define MDEMOD_HIP_HOST_H
@@ -11,6 +11,7 @@
 #include <utility>
 #include <vector>
 
+#include "buffers.h"
 #include "mdemod_internal_api.h"
 
 /* A hipError_t becomes the entry's return value: the text for mdemod_last_error(), the pending error dropped (it is reported: it
@@ -40,15 +41,6 @@ mdm_select_device(int device)
 		return MDEMOD_ERR_HIP;
 	}
 	return MDEMOD_OK;
-}
-
-/* Do two byte ranges overlap?  What every device entry asks of its outputs against its inputs and each other (the blocks of one
- * launch would read what others write).  A range that is not there (NULL, or no bytes) overlaps nothing. */
-inline bool
-mdm_ranges_intersect(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-	return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
 }
 
 /* Device memory with one owner: everything it handed out is freed when it goes (a context's owner with the context, a call's with

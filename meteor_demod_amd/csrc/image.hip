@@ -111,8 +111,6 @@ image_decode(const uint8_t *vcdu, uint32_t n, const mdemod_packet *desc, uint32_
 
 namespace {
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 int
 find_run(const mdemod_image_opts &o, const uint8_t *vcdu_dev, const mdemod_rs_info *info_dev, uint64_t n, mdemod_packet *desc_dev, uint64_t cap,
          uint64_t *total_dev, hipStream_t st)
@@ -199,9 +197,7 @@ try { MDEMOD_API_ENTER
 			REFUSE("mdemod_packets_find_device: the VCDUs, the report and the descriptors must stand at multiples of 4 bytes, the total at a multiple of 8");
 		if (n > IMG_MAX_FRAMES) REFUSE("image: %llu frames are more than one batch takes (2^20)", (unsigned long long)n);
 		const uint64_t in_bytes = n * IMG_VCDU, info_bytes = n * sizeof(mdemod_rs_info), out_bytes = (n ? cap : 0) * sizeof(mdemod_packet);
-		if (mdm_ranges_intersect(vcdu_dev, in_bytes, desc_dev, out_bytes) || mdm_ranges_intersect(vcdu_dev, in_bytes, total_dev, 8) ||
-		    mdm_ranges_intersect(info_dev, info_bytes, desc_dev, out_bytes) || mdm_ranges_intersect(info_dev, info_bytes, total_dev, 8) ||
-		    mdm_ranges_intersect(desc_dev, out_bytes, total_dev, 8))
+		if (!MdmBuffers().in(vcdu_dev, in_bytes).in(info_dev, info_bytes).out(desc_dev, out_bytes).out(total_dev, 8).apart())
 			REFUSE("mdemod_packets_find_device: the VCDUs, the report, the descriptors and the total intersect");
 	}
 	rc = mdm_select_device(device);
@@ -224,9 +220,7 @@ try { MDEMOD_API_ENTER
 	if (n_desc > 0x7FFFFFFFull) REFUSE("image: %llu descriptors are more than one launch takes", (unsigned long long)n_desc);
 	const uint64_t in_bytes = n * IMG_VCDU, desc_bytes = n_desc * sizeof(mdemod_packet), strip_bytes = n_desc * MDEMOD_IMAGE_STRIP_BYTES,
 	               sinfo_bytes = n_desc * sizeof(mdemod_strip_info);
-	if (mdm_ranges_intersect(vcdu_dev, in_bytes, strips_dev, strip_bytes) || mdm_ranges_intersect(vcdu_dev, in_bytes, sinfo_dev, sinfo_bytes) ||
-	    mdm_ranges_intersect(desc_dev, desc_bytes, strips_dev, strip_bytes) || mdm_ranges_intersect(desc_dev, desc_bytes, sinfo_dev, sinfo_bytes) ||
-	    mdm_ranges_intersect(strips_dev, strip_bytes, sinfo_dev, sinfo_bytes))
+	if (!MdmBuffers().in(vcdu_dev, in_bytes).in(desc_dev, desc_bytes).out(strips_dev, strip_bytes).out(sinfo_dev, sinfo_bytes).apart())
 		REFUSE("mdemod_image_decode_device: the VCDUs, the descriptors, the strips and the reports intersect (the lanes of one launch would read what others write)");
 	rc = mdm_select_device(device);
 	if (rc) return rc;

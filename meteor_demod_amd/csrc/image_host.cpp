@@ -10,8 +10,6 @@
 #include "image_host.h"
 #include "mdemod_internal_api.h"
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 namespace {
 
 constexpr ImgTables TAB = img_make_tables();

@@ -175,8 +175,6 @@ il_deinterleave(const int8_t *soft, uint64_t m, uint64_t step, uint64_t P, uint6
 
 namespace {
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 /* the weight words of il_candidates: bytes (I_k, Q_k, I_k+1, Q_k+1) against the pattern on one rail, zeros on the other */
 IlcWeights
 ilc_weights()

@@ -11,8 +11,6 @@
 #include "interleave_host.h"
 #include "mdemod_internal_api.h"
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 namespace {
 
 /* rail `rail` (0: I", 1: Q") of symbol i of soft[m][2] through the combined hypothesis H = h + 8 s, in int32: I' and Q' are the

@@ -15,22 +15,21 @@
  *   ballot of the FF bytes and a popcount below the lane give every byte its place behind the 00s before it.  The length pass
  *   keeps the count; the write pass, the same code, stores the bytes and the marker behind them at the segment's final offset.
  *   LDS: 208 bytes per block (the header derives it), 39 936 bytes for 64 colour MCUs, and 2176 bytes of codes.
- * jpeg_offsets: one block of 1024 threads walks the lengths in chunks of 1024 with a carry: offsets in 64 bits, the total, whether
- *   it fits; it also stores the file's head and EOI, which the host made.  No global atomics anywhere.
+ * jpeg_offsets: one block runs the encoders' offset scan (csrc/encoder_device.h) over the lengths, each with its marker: the total,
+ *   whether it fits; it also stores the file's head and EOI, which the host made.  No global atomics anywhere.
+ * The check of the entries' pointers, mdemod_jpeg_result and the host entry's download are the PNG encoder's too (csrc/encoder_device.h).
  */
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <cstring>
 
 #include "jpeg_host.h"
-#include "hip_host.h"
+#include "encoder_device.h"
 
 #define JT_THREADS 256
 #define JT_MCUS    32                             /* MCUs of a strip */
 #define JT_PITCH   65                             /* words of t per block */
 #define JE_THREADS 64
-#define JS_THREADS 1024
 
 static_assert(MDEMOD_JPEG_MAX_RESTART <= JE_THREADS, "a lane per MCU of a segment");
 static_assert(MDEMOD_JPEG_BLOCK_BYTES * 8 >= 22 + 63 * 26 && MDEMOD_JPEG_BLOCK_BYTES % 4 == 0, "the bits of a block fit, in whole words");
@@ -247,45 +246,20 @@ struct JpegHead {
 	uint8_t b[JPEG_HEAD_ROOM];
 };
 
-__global__ void __launch_bounds__(JS_THREADS)
+__global__ void __launch_bounds__(ENC_SCAN_THREADS)
 jpeg_offsets(const uint32_t *seg_len, uint64_t *seg_off, uint32_t n_seg, uint8_t *out, uint64_t out_room, uint64_t *result, JpegHead head)
 {
-	__shared__ uint32_t sums[JS_THREADS / 64];
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	uint64_t carry = head.n;
-	for (uint32_t chunk = 0; chunk < n_seg; chunk += JS_THREADS) {
-		const uint32_t i = chunk + tid;
-		const uint32_t mine = i < n_seg ? seg_len[i] + 2u : 0u;                  /* the segment and the marker behind it */
-		uint32_t incl = mine;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t up = __shfl_up(incl, d, 64);
-			if (lane >= static_cast<uint32_t>(d)) incl += up;
-		}
-		__syncthreads();                                                         /* (the sums of the chunk before have been read) */
-		if (lane == 63u) sums[wave] = incl;
-		__syncthreads();
-		uint32_t before = 0, all = 0;
-#pragma unroll
-		for (uint32_t k = 0; k < JS_THREADS / 64; k++) {
-			const uint32_t s = sums[k];
-			if (k < wave) before += s;
-			all += s;
-		}
-		if (i < n_seg) seg_off[i] = carry + before + incl - mine;
-		carry += all;
-	}
+	const uint32_t tid = threadIdx.x;
+	const uint64_t carry = enc_scan_offsets(seg_len, seg_off, n_seg, 2u, head.n);  /* a segment and the marker behind it */
 	const uint64_t total = carry - 2u + (head.n ? 2u : 0u);                       /* no marker behind the last segment; EOI */
 	const bool fits = total <= out_room;
 	if (tid == 0) { seg_off[n_seg] = total; result[0] = total; result[1] = fits; }
 	if (!fits || !head.n) return;
-	for (uint32_t i = tid; i < head.n; i += JS_THREADS) out[i] = head.b[i];
+	for (uint32_t i = tid; i < head.n; i += ENC_SCAN_THREADS) out[i] = head.b[i];
 	if (tid == 0) { out[total - 2] = 0xFF; out[total - 1] = 0xD9; }
 }
 
 namespace {
-
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
 
 struct JpegWork {
 	int16_t *coef;
@@ -337,31 +311,13 @@ entropy_run(const int16_t *coef, uint64_t n_mcus, uint32_t planes, uint32_t ri, 
 	}
 	JpegHead none;
 	memset(&none, 0, sizeof none);
-	hipLaunchKernelGGL(jpeg_offsets, dim3(1), dim3(JS_THREADS), 0, st, w.seg_len, w.seg_off, a.n_seg, out, out_room, result, head ? *head : none);
+	hipLaunchKernelGGL(jpeg_offsets, dim3(1), dim3(ENC_SCAN_THREADS), 0, st, w.seg_len, w.seg_off, a.n_seg, out, out_room, result, head ? *head : none);
 	HIP_TRY(hipGetLastError());
 	if (write) {
 		if (planes == 3) hipLaunchKernelGGL((jpeg_entropy<3, true>), grid, block, lds, st, a);
 		else hipLaunchKernelGGL((jpeg_entropy<1, true>), grid, block, lds, st, a);
 		HIP_TRY(hipGetLastError());
 	}
-	return MDEMOD_OK;
-}
-
-/* the pointers of a device entry: there, aligned, apart */
-int
-check_buffers(const char *who, const void *in, uint64_t in_bytes, uint64_t in_align, const uint8_t *out, uint64_t out_room, const uint64_t *result, const void *work,
-              uint64_t work_bytes, uint64_t work_need)
-{
-	if (!in) REFUSE("%s: the input is needed", who);
-	if (!out && out_room) REFUSE("%s: the output is needed", who);
-	if (!result) REFUSE("%s: the result is needed", who);
-	if (!work) REFUSE("%s: the workspace is needed", who);
-	if (work_bytes < work_need) REFUSE("%s: the workspace needs %llu bytes, not %llu", who, static_cast<unsigned long long>(work_need), static_cast<unsigned long long>(work_bytes));
-	if ((reinterpret_cast<uintptr_t>(work) & 15u) || (reinterpret_cast<uintptr_t>(in) & (in_align - 1))) REFUSE("%s: the workspace and the coefficients must stand at multiples of 16 bytes", who);
-	if (reinterpret_cast<uintptr_t>(result) & 7u) REFUSE("%s: the result must stand at a multiple of 8 bytes", who);
-	const bool hit = mdm_ranges_intersect(out, out_room, in, in_bytes) || mdm_ranges_intersect(work, work_bytes, in, in_bytes) || mdm_ranges_intersect(result, 16, in, in_bytes) ||
-	                 mdm_ranges_intersect(out, out_room, work, work_bytes) || mdm_ranges_intersect(out, out_room, result, 16) || mdm_ranges_intersect(work, work_bytes, result, 16);
-	if (hit) REFUSE("%s: the output, the workspace, the result and the input intersect", who);
 	return MDEMOD_OK;
 }
 
@@ -377,8 +333,8 @@ try { MDEMOD_API_ENTER
 	int rc = jpeg_check_picture(who, width, height, planes, quality, restart_interval);
 	if (rc) return rc;
 	const uint64_t n_mcus = jpeg_mcus(width, height), coef_bytes = n_mcus * planes * 128;
-	if ((rc = check_buffers(who, picture_dev, static_cast<uint64_t>(width) * height * planes, 1, out_dev, out_room, result_dev, work_dev, work_bytes,
-	                        mdemod_jpeg_workspace(width, height, planes, restart_interval))))
+	if ((rc = enc_check_buffers(who, "coefficients", picture_dev, static_cast<uint64_t>(width) * height * planes, 1, nullptr, 0, out_dev, out_room, result_dev, work_dev,
+	                            work_bytes, mdemod_jpeg_workspace(width, height, planes, restart_interval))))
 		return rc;
 	if ((rc = mdm_select_device(device))) return rc;
 	const uint32_t ri = jpeg_interval(restart_interval);
@@ -397,8 +353,8 @@ try { MDEMOD_API_ENTER
 	const char *who = "mdemod_jpeg_entropy_device";
 	int rc = jpeg_check_entropy(who, n_mcus, planes, restart_interval);
 	if (rc) return rc;
-	if ((rc = check_buffers(who, coef_dev, n_mcus * planes * 128, 16, out_dev, out_room, result_dev, work_dev, work_bytes,
-	                        mdemod_jpeg_entropy_workspace(n_mcus, restart_interval))))
+	if ((rc = enc_check_buffers(who, "coefficients", coef_dev, n_mcus * planes * 128, 16, nullptr, 0, out_dev, out_room, result_dev, work_dev, work_bytes,
+	                            mdemod_jpeg_entropy_workspace(n_mcus, restart_interval))))
 		return rc;
 	if ((rc = mdm_select_device(device))) return rc;
 	const uint32_t ri = jpeg_interval(restart_interval);
@@ -409,18 +365,7 @@ try { MDEMOD_API_ENTER
 int
 mdemod_jpeg_result(const uint64_t *result_dev, uint64_t *bytes, int device, void *hip_stream)
 try { MDEMOD_API_ENTER
-	if (!result_dev) REFUSE("mdemod_jpeg_result: the result is needed");
-	int rc = mdm_select_device(device);
-	if (rc) return rc;
-	uint64_t r[2] = { 0, 0 };
-	HIP_TRY(hipMemcpyAsync(r, result_dev, sizeof r, hipMemcpyDeviceToHost, static_cast<hipStream_t>(hip_stream)));
-	HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(hip_stream)));
-	if (bytes) *bytes = r[0];
-	if (!r[1]) {
-		mdm_note_error("mdemod_jpeg_result: the output needs %llu bytes and out_room was less; nothing was written", static_cast<unsigned long long>(r[0]));
-		return MDEMOD_ERR_OVERFLOW;
-	}
-	return MDEMOD_OK;
+	return enc_result("mdemod_jpeg_result", result_dev, bytes, device, hip_stream);
 } MDEMOD_API_CATCH
 
 int
@@ -453,12 +398,7 @@ try { MDEMOD_API_ENTER
 	mem.release(d_picture);
 	if ((rc = mem.alloc(&d_out, r[0]))) return rc;
 	if ((rc = entropy_run(w.coef, n_mcus, planes, ri, d_out, r[0], d_result, w, &head, false, true, nullptr))) return rc;
-	uint8_t *host = static_cast<uint8_t *>(malloc(r[0]));
-	if (!host) { mdm_note_error("%s: no memory for a file of %llu bytes", who, static_cast<unsigned long long>(r[0])); return MDEMOD_ERR_NOMEM; }
-	const hipError_t e = hipMemcpy(host, d_out, r[0], hipMemcpyDeviceToHost);
-	if (e != hipSuccess) { free(host); HIP_TRY(e); }
-	*file = host; *bytes = r[0];
-	return MDEMOD_OK;
+	return enc_download(who, d_out, r[0], file, bytes);
 } MDEMOD_API_CATCH
 
 } /* extern "C" */

@@ -8,9 +8,7 @@
 #include <vector>
 
 #include "jpeg_host.h"
-#include "mdemod_internal_api.h"
-
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
+#include "encoder_host.h"
 
 namespace {
 
@@ -79,18 +77,6 @@ model_segments(const int16_t *coef, uint64_t n_mcus, uint32_t planes, uint32_t r
 		w.flush();
 		if (s + 1 < n_seg) { out.push_back(0xFF); out.push_back(static_cast<uint8_t>(0xD0 + (s & 7))); }
 	}
-}
-
-int
-give(const char *who, const std::vector<uint8_t> &file, uint8_t *out, uint64_t out_room, uint64_t *bytes)
-{
-	if (bytes) *bytes = file.size();
-	if (file.size() > out_room) {
-		mdm_note_error("%s: the output needs %llu bytes, out_room is %llu", who, static_cast<unsigned long long>(file.size()), static_cast<unsigned long long>(out_room));
-		return MDEMOD_ERR_OVERFLOW;
-	}
-	if (!file.empty()) memcpy(out, file.data(), file.size());
-	return MDEMOD_OK;
 }
 
 } /* namespace */
@@ -249,7 +235,7 @@ try { MDEMOD_API_ENTER
 	if (!coef || (!out && out_room)) REFUSE("%s: the coefficients and the output are needed", who);
 	std::vector<uint8_t> file;
 	model_segments(coef, n_mcus, planes, jpeg_interval(restart_interval), file);
-	return give(who, file, out, out_room, bytes);
+	return enc_give(who, file, out, out_room, bytes);
 } MDEMOD_API_CATCH
 
 int
@@ -267,7 +253,7 @@ try { MDEMOD_API_ENTER
 	file.resize(jpeg_head(width, height, planes, quality, restart_interval, file.data()));
 	model_segments(coef.data(), n_mcus, planes, jpeg_interval(restart_interval), file);
 	file.push_back(0xFF); file.push_back(0xD9);
-	return give(who, file, out, out_room, bytes);
+	return enc_give(who, file, out, out_room, bytes);
 } MDEMOD_API_CATCH
 
 } /* extern "C" */

@@ -78,8 +78,6 @@ map_warp(MapWarp a)
 
 namespace {
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 int
 warp_run(const uint8_t *const image[3], const uint8_t *const filled[3], uint32_t rows, const uint32_t *select, uint32_t planes, const uint8_t *lut_dev,
          const int32_t *nodes_dev, uint32_t width, uint32_t height, uint8_t *out_dev, uint8_t *valid_dev, hipStream_t st)
@@ -110,18 +108,11 @@ warp_entry(const char *who, const uint8_t *const image_dev[3], const uint8_t *co
 	uintptr_t low = reinterpret_cast<uintptr_t>(lut_dev) | reinterpret_cast<uintptr_t>(nodes_dev) | reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(valid_dev);
 	for (uint32_t p = 0; p < planes; p++) low |= reinterpret_cast<uintptr_t>(image_dev[select[p]]);
 	if (low & 3u) REFUSE("%s: the pictures, the tables, the nodes and the outputs must stand at multiples of 4 bytes", who);
-	const uint64_t out_bytes = static_cast<uint64_t>(height) * width * planes, valid_bytes = valid_dev ? static_cast<uint64_t>(height) * width : 0;
-	const uint64_t node_bytes = 8ull * map_node_count(height) * map_node_count(width), lut_bytes = 256 * planes;
-	const void *outs[2] = { out_dev, valid_dev };
-	const uint64_t out_sizes[2] = { out_bytes, valid_bytes };
-	bool hit = mdm_ranges_intersect(out_dev, out_bytes, valid_dev, valid_bytes);
-	for (int k = 0; k < 2; k++) {
-		hit = hit || mdm_ranges_intersect(outs[k], out_sizes[k], lut_dev, lut_bytes) || mdm_ranges_intersect(outs[k], out_sizes[k], nodes_dev, node_bytes);
-		for (uint32_t p = 0; p < planes; p++)
-			hit = hit || mdm_ranges_intersect(outs[k], out_sizes[k], image_dev[select[p]], rows * PIC_LINE_BYTES) ||
-			      mdm_ranges_intersect(outs[k], out_sizes[k], filled_dev[select[p]], static_cast<uint64_t>(rows) * PIC_CELLS);
-	}
-	if (hit) REFUSE("%s: the outputs and the inputs intersect (the blocks of one launch would read what others write)", who);
+	const uint64_t area = static_cast<uint64_t>(height) * width;
+	MdmBuffers b;
+	b.in(lut_dev, 256 * planes).in(nodes_dev, 8ull * map_node_count(height) * map_node_count(width)).out(out_dev, area * planes).out(valid_dev, area);
+	for (uint32_t p = 0; p < planes; p++) b.in(image_dev[select[p]], rows * PIC_LINE_BYTES).in(filled_dev[select[p]], static_cast<uint64_t>(rows) * PIC_CELLS);
+	if (!b.apart()) REFUSE("%s: the outputs and the inputs intersect (the blocks of one launch would read what others write)", who);
 	if ((rc = mdm_select_device(device))) return rc;
 	return warp_run(image_dev, filled_dev, rows, select, planes, lut_dev, nodes_dev, width, height, out_dev, valid_dev, static_cast<hipStream_t>(hip_stream));
 }

@@ -22,8 +22,6 @@
 #include "mdemod_internal_api.h"
 #include "warp_model.h"
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 namespace {
 
 constexpr double MAP_MU = 398600.4418, MAP_RE = 6378.137, MAP_F = 1.0 / 298.257223563, MAP_J2 = 1.08262668e-3;

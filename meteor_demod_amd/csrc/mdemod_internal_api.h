@@ -19,6 +19,8 @@
  * int-returning entry, empties it when the OUTERMOST entry on this thread begins, so a text never outlives the call it belongs to
  * (entries call each other: mdemod_create -> mdemod_reset / mdemod_destroy). */
 void mdm_note_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+/* an argument check that fails: the text, and the entry (or the helper whose status the entry returns) ends */
+#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
 struct mdm_api_scope { mdm_api_scope(); ~mdm_api_scope(); };
 #define MDEMOD_API_ENTER mdm_api_scope api_scope_;
 #define MDEMOD_API_CATCH catch (...) { mdm_note_error("a C++ exception reached the boundary (allocation failed, or a thread could not be started)"); return MDEMOD_ERR_NOMEM; }

@@ -132,8 +132,6 @@ mosaic_blend(MosaicBlend a)
 
 namespace {
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 /* nodes of every pass: from the band's first node row on */
 int
 blend_run(const mdemod_mosaic_source *sources, uint32_t n, const uint32_t *select, uint32_t planes, uint32_t blend, uint32_t width, uint32_t height,
@@ -173,21 +171,16 @@ blend_entry(const char *who, const mdemod_mosaic_source *sources, uint32_t n, co
 	}
 	if (low & 3u) REFUSE("%s: the pictures, the tables, the nodes and the outputs must stand at multiples of 4 bytes", who);
 	const uint64_t area = static_cast<uint64_t>(height) * width;
-	const void *outs[3] = { out_dev, valid_dev, cover_dev };
-	const uint64_t out_sizes[3] = { area * planes, valid_dev ? area : 0, cover_dev ? area : 0 };
-	const uint64_t node_bytes = 8ull * map_node_count(height) * map_node_count(width), lut_bytes = 256 * planes;
-	bool hit = mdm_ranges_intersect(out_dev, out_sizes[0], valid_dev, out_sizes[1]) || mdm_ranges_intersect(out_dev, out_sizes[0], cover_dev, out_sizes[2]) ||
-	           mdm_ranges_intersect(valid_dev, out_sizes[1], cover_dev, out_sizes[2]);
-	for (int o = 0; o < 3; o++)
-		for (uint32_t k = 0; k < n; k++) {
-			const mdemod_mosaic_source &s = sources[k];
-			if (!s.rows) continue;
-			hit = hit || mdm_ranges_intersect(outs[o], out_sizes[o], s.lut, lut_bytes) || mdm_ranges_intersect(outs[o], out_sizes[o], s.nodes, node_bytes);
-			for (uint32_t p = 0; p < planes; p++)
-				hit = hit || mdm_ranges_intersect(outs[o], out_sizes[o], s.image[select[p]], s.rows * PIC_LINE_BYTES) ||
-				      mdm_ranges_intersect(outs[o], out_sizes[o], s.filled[select[p]], static_cast<uint64_t>(s.rows) * PIC_CELLS);
-		}
-	if (hit) REFUSE("%s: the outputs and the inputs intersect (the blocks of one launch would read what others write)", who);
+	const uint64_t node_bytes = 8ull * map_node_count(height) * map_node_count(width);
+	MdmBuffers b;
+	b.out(out_dev, area * planes).out(valid_dev, area).out(cover_dev, area);
+	for (uint32_t k = 0; k < n; k++) {
+		const mdemod_mosaic_source &s = sources[k];
+		if (!s.rows) continue;
+		b.in(s.lut, 256 * planes).in(s.nodes, node_bytes);
+		for (uint32_t p = 0; p < planes; p++) b.in(s.image[select[p]], s.rows * PIC_LINE_BYTES).in(s.filled[select[p]], static_cast<uint64_t>(s.rows) * PIC_CELLS);
+	}
+	if (!b.apart()) REFUSE("%s: the outputs and the inputs intersect (the blocks of one launch would read what others write)", who);
 	if ((rc = mdm_select_device(device))) return rc;
 	return blend_run(sources, n, select, planes, blend, width, height, out_dev, valid_dev, cover_dev, static_cast<hipStream_t>(hip_stream));
 }

@@ -12,8 +12,6 @@
 #include "mdemod_internal_api.h"
 #include "warp_model.h"
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 namespace {
 
 void

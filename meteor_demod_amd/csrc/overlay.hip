@@ -146,8 +146,6 @@ overlay_draw(OverlayDraw a)
 
 namespace {
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 /* `height` lines from line `line0` of the picture the bins were made for; tile_first of that line's tile row */
 int
 draw_run(const mdemod_overlay_piece *pieces_dev, uint64_t n_pieces, const uint32_t *tile_first_dev, const uint32_t *items_dev, uint64_t n_items,
@@ -251,17 +249,10 @@ try { MDEMOD_API_ENTER
 	if (low & 3u) REFUSE("%s: the pieces, the bins, the picture, valid and mask must stand at multiples of 4 bytes", who);
 	const uint64_t area = static_cast<uint64_t>(height) * width;
 	const uint64_t tiles = static_cast<uint64_t>(overlay_tiles(width)) * overlay_tiles(height);
-	const void *outs[2] = { pixels_dev, mask_dev };
-	const uint64_t out_sizes[2] = { area * planes, mask_dev ? area : 0 };
-	bool hit = mdm_ranges_intersect(pixels_dev, out_sizes[0], mask_dev, out_sizes[1]);
-	for (int o = 0; o < 2; o++) {
-		hit = hit || mdm_ranges_intersect(outs[o], out_sizes[o], valid_dev, valid_dev ? area : 0);
-		if (!draws) continue;
-		hit = hit || mdm_ranges_intersect(outs[o], out_sizes[o], pieces_dev, n_pieces * sizeof(mdemod_overlay_piece)) ||
-		      mdm_ranges_intersect(outs[o], out_sizes[o], tile_first_dev, (tiles + 1) * sizeof(uint32_t)) ||
-		      mdm_ranges_intersect(outs[o], out_sizes[o], items_dev, n_items * sizeof(uint32_t));
-	}
-	if (hit) REFUSE("%s: the outputs and the inputs intersect (the blocks of one launch would read what others write)", who);
+	MdmBuffers b;
+	b.out(pixels_dev, area * planes).out(mask_dev, area).in(valid_dev, area);
+	if (draws) b.in(pieces_dev, n_pieces * sizeof(mdemod_overlay_piece)).in(tile_first_dev, (tiles + 1) * sizeof(uint32_t)).in(items_dev, n_items * sizeof(uint32_t));
+	if (!b.apart()) REFUSE("%s: the outputs and the inputs intersect (the blocks of one launch would read what others write)", who);
 	if ((rc = mdm_select_device(device))) return rc;
 	return draw_run(pieces_dev, n_pieces, tile_first_dev, items_dev, n_items, styles, n_styles, width, 0, height, planes, pixels_dev, valid_dev, mask_dev,
 	                static_cast<hipStream_t>(hip_stream));

@@ -14,8 +14,6 @@
 #include "overlay_host.h"
 #include "mdemod_internal_api.h"
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 namespace {
 
 constexpr int64_t VERTEX_TOP = MDEMOD_OVERLAY_VERTEX_TOP;

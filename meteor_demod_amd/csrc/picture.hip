@@ -128,19 +128,6 @@ picture_render(PicRender a)
 
 namespace {
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
-/* an output against every input slot that is there */
-bool
-pic_hits_slots(const void *out, uint64_t out_bytes, const uint8_t *const image[3], const uint8_t *const filled[3], uint32_t rows)
-{
-	for (int s = 0; s < 3; s++)
-		if (mdm_ranges_intersect(out, out_bytes, image[s], rows * PIC_LINE_BYTES) ||
-		    mdm_ranges_intersect(out, out_bytes, filled[s], static_cast<uint64_t>(rows) * PIC_CELLS))
-			return true;
-	return false;
-}
-
 int
 histogram_run(const uint8_t *const image[3], const uint8_t *const filled[3], uint32_t rows, uint32_t *hist_dev, hipStream_t st)
 {
@@ -242,7 +229,9 @@ try { MDEMOD_API_ENTER
 			if (image_dev[s] && !filled_dev[s]) REFUSE("mdemod_picture_histogram_device: the mask of slot %d is needed", s);
 			if (reinterpret_cast<uintptr_t>(image_dev[s]) & 3u) REFUSE("mdemod_picture_histogram_device: the pictures must stand at multiples of 4 bytes");
 		}
-		if (pic_hits_slots(hist_dev, 3 * 256 * sizeof(uint32_t), image_dev, filled_dev, rows))
+		MdmBuffers b;
+		for (int s = 0; s < 3; s++) b.in(image_dev[s], rows * PIC_LINE_BYTES).in(filled_dev[s], static_cast<uint64_t>(rows) * PIC_CELLS);
+		if (!b.out(hist_dev, 3 * 256 * sizeof(uint32_t)).apart())
 			REFUSE("mdemod_picture_histogram_device: the histogram and the inputs intersect");
 	}
 	const int rc = mdm_select_device(device);
@@ -265,12 +254,9 @@ try { MDEMOD_API_ENTER
 	for (uint32_t p = 0; p < planes; p++) low |= reinterpret_cast<uintptr_t>(image_dev[select[p]]);
 	if (low & 3u) REFUSE("mdemod_picture_render_device: the pictures, the tables, the map and the outputs must stand at multiples of 4 bytes");
 	const uint64_t out_bytes = 8ull * rows * width * planes, valid_bytes = valid_dev ? static_cast<uint64_t>(rows) * width : 0;
-	const uint8_t *img[3] = { nullptr, nullptr, nullptr }, *fil[3] = { nullptr, nullptr, nullptr };
-	for (uint32_t p = 0; p < planes; p++) { img[select[p]] = image_dev[select[p]]; fil[select[p]] = filled_dev[select[p]]; }
-	if (pic_hits_slots(out_dev, out_bytes, img, fil, rows) || pic_hits_slots(valid_dev, valid_bytes, img, fil, rows) ||
-	    mdm_ranges_intersect(out_dev, out_bytes, lut_dev, 256 * planes) || mdm_ranges_intersect(out_dev, out_bytes, map_dev, 4ull * width) ||
-	    mdm_ranges_intersect(valid_dev, valid_bytes, lut_dev, 256 * planes) || mdm_ranges_intersect(valid_dev, valid_bytes, map_dev, 4ull * width) ||
-	    mdm_ranges_intersect(out_dev, out_bytes, valid_dev, valid_bytes))
+	MdmBuffers b;
+	for (uint32_t p = 0; p < planes; p++) b.in(image_dev[select[p]], rows * PIC_LINE_BYTES).in(filled_dev[select[p]], static_cast<uint64_t>(rows) * PIC_CELLS);
+	if (!b.in(lut_dev, 256 * planes).in(map_dev, 4ull * width).out(out_dev, out_bytes).out(valid_dev, valid_bytes).apart())
 		REFUSE("mdemod_picture_render_device: the outputs and the inputs intersect (the blocks of one launch would read what others write)");
 	if ((rc = mdm_select_device(device))) return rc;
 	return render_run(image_dev, filled_dev, rows, select, planes, lut_dev, map_dev, width, out_dev, valid_dev, static_cast<hipStream_t>(hip_stream));

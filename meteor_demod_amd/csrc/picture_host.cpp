@@ -11,8 +11,6 @@
 #include "picture_host.h"
 #include "mdemod_internal_api.h"
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 namespace {
 
 constexpr double PIC_R = 6371.0, PIC_PI = 3.14159265358979323846;

@@ -18,17 +18,17 @@
  *   by x^(8 n) for the n bytes behind its slice, and the products are XORed.  The chunk leaves as whole words into the segment's
  *   slot of the workspace.
  *   LDS: the segment at its pitch (33 792 bytes for 32 KiB), the image (32 KiB + 32), 10 KiB of tables: 75 KiB, two blocks a CU.
- * png_offsets: one block of PNG_SCAN_THREADS threads walks the lengths in chunks with a carry: offsets in 64 bits, the total, whether
- *   it fits; it sums the segments' Adler parts and stores the file's head, the Adler chunk and IEND.  No global atomics anywhere.
+ * png_offsets: one block runs the encoders' offset scan (csrc/encoder_device.h) over the lengths: the total, whether it fits; it sums
+ *   the segments' Adler parts and stores the file's head, the Adler chunk and IEND.  No global atomics anywhere.
  * png_place: a block per segment copies the chunk from its slot to its offset.
+ * The check of the entries' pointers, mdemod_png_result and the host entry's download are the JPEG encoder's too (csrc/encoder_device.h).
  */
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <cstring>
 
 #include "png_host.h"
-#include "hip_host.h"
+#include "encoder_device.h"
 
 #define PF_THREADS 256
 #define PF_TILE    1024                           /* pixels of a tile */
@@ -378,47 +378,23 @@ struct PngEnds {
 	uint8_t head[MDEMOD_PNG_HEAD + 1];
 };
 
-__global__ void __launch_bounds__(PNG_SCAN_THREADS)
+__global__ void __launch_bounds__(ENC_SCAN_THREADS)
 png_offsets(const uint32_t *seg_len, const uint32_t *adler, uint64_t *seg_off, uint32_t n_seg, uint64_t n_bytes, uint8_t *out, uint64_t out_room, uint64_t *result,
             PngEnds ends)
 {
-	__shared__ uint32_t sums[PNG_SCAN_THREADS / 64];
 	__shared__ uint32_t sum_a, sum_b;
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	uint64_t carry = ends.n;
-	uint32_t my_a = 0, my_b = 0;
+	const uint32_t tid = threadIdx.x;
 	if (tid == 0) { sum_a = 0; sum_b = 0; }
-	for (uint32_t chunk = 0; chunk < n_seg; chunk += PNG_SCAN_THREADS) {
-		const uint32_t i = chunk + tid;
-		const uint32_t mine = i < n_seg ? seg_len[i] : 0u;
-		if (i < n_seg) { my_a = (my_a + adler[2 * i]) % PNG_ADLER; my_b = (my_b + adler[2 * i + 1]) % PNG_ADLER; }
-		uint32_t incl = mine;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t upv = __shfl_up(incl, d, 64);
-			if (lane >= static_cast<uint32_t>(d)) incl += upv;
-		}
-		__syncthreads();                                                         /* (the sums of the chunk before have been read) */
-		if (lane == 63u) sums[wave] = incl;
-		__syncthreads();
-		uint32_t before = 0, all = 0;
-#pragma unroll
-		for (uint32_t k = 0; k < PNG_SCAN_THREADS / 64; k++) {
-			const uint32_t s = sums[k];
-			if (k < wave) before += s;
-			all += s;
-		}
-		if (i < n_seg) seg_off[i] = carry + before + incl - mine;
-		carry += all;
-	}
-	const uint64_t total = carry + (ends.n ? MDEMOD_PNG_TAIL : 0u);
+	const uint64_t total = enc_scan_offsets(seg_len, seg_off, n_seg, 0u, ends.n) + (ends.n ? MDEMOD_PNG_TAIL : 0u);
 	const bool fits = total <= out_room;
 	if (tid == 0) { seg_off[n_seg] = total; result[0] = total; result[1] = fits; }
 	if (!fits || !ends.n) return;                                                 /* (uniform) */
+	uint32_t my_a = 0, my_b = 0;
+	for (uint32_t i = tid; i < n_seg; i += ENC_SCAN_THREADS) { my_a = (my_a + adler[2 * i]) % PNG_ADLER; my_b = (my_b + adler[2 * i + 1]) % PNG_ADLER; }
 	__syncthreads();
 	atomicAdd(&sum_a, my_a);
 	atomicAdd(&sum_b, my_b);
-	for (uint32_t i = tid; i < ends.n; i += PNG_SCAN_THREADS) out[i] = ends.head[i];
+	for (uint32_t i = tid; i < ends.n; i += ENC_SCAN_THREADS) out[i] = ends.head[i];
 	__syncthreads();
 	if (tid) return;
 	const uint32_t s1 = (1u + sum_a) % PNG_ADLER, s2 = static_cast<uint32_t>((n_bytes % PNG_ADLER + sum_b) % PNG_ADLER);
@@ -446,8 +422,6 @@ png_place(const uint8_t *slots, uint32_t slot_bytes, const uint32_t *seg_len, co
 }
 
 namespace {
-
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
 
 struct PngWork {
 	uint8_t *filtered, *slots;
@@ -501,32 +475,10 @@ deflate_run(const uint8_t *bytes, uint64_t n_bytes, uint32_t seg_bytes, uint8_t 
 	HIP_TRY(mdm_launch(png_deflate, dim3(a.n_seg), dim3(PD_THREADS), lds, st, a));
 	PngEnds none;
 	memset(&none, 0, sizeof none);
-	hipLaunchKernelGGL(png_offsets, dim3(1), dim3(PNG_SCAN_THREADS), 0, st, w.seg_len, w.adler, w.seg_off, a.n_seg, n_bytes, out, out_room, result, ends ? *ends : none);
+	hipLaunchKernelGGL(png_offsets, dim3(1), dim3(ENC_SCAN_THREADS), 0, st, w.seg_len, w.adler, w.seg_off, a.n_seg, n_bytes, out, out_room, result, ends ? *ends : none);
 	HIP_TRY(hipGetLastError());
 	hipLaunchKernelGGL(png_place, dim3(a.n_seg), dim3(PP_THREADS), 0, st, w.slots, a.slot_bytes, w.seg_len, w.seg_off, a.n_seg, out, out_room);
 	HIP_TRY(hipGetLastError());
-	return MDEMOD_OK;
-}
-
-/* the pointers of a device entry: there, aligned, apart */
-int
-check_buffers(const char *who, const void *in, uint64_t in_bytes, uint64_t in_align, const void *in2, uint64_t in2_bytes, const uint8_t *out, uint64_t out_room,
-              const uint64_t *result, const void *work, uint64_t work_bytes, uint64_t work_need)
-{
-	if (!in) REFUSE("%s: the input is needed", who);
-	if (!out && out_room) REFUSE("%s: the output is needed", who);
-	if (!result) REFUSE("%s: the result is needed", who);
-	if (!work) REFUSE("%s: the workspace is needed", who);
-	if (work_bytes < work_need) REFUSE("%s: the workspace needs %llu bytes, not %llu", who, static_cast<unsigned long long>(work_need), static_cast<unsigned long long>(work_bytes));
-	if ((reinterpret_cast<uintptr_t>(work) & 15u) || (reinterpret_cast<uintptr_t>(in) & (in_align - 1))) REFUSE("%s: the workspace and the bytes must stand at multiples of 16 bytes", who);
-	if (reinterpret_cast<uintptr_t>(result) & 7u) REFUSE("%s: the result must stand at a multiple of 8 bytes", who);
-	bool hit = mdm_ranges_intersect(out, out_room, work, work_bytes) || mdm_ranges_intersect(out, out_room, result, 16) || mdm_ranges_intersect(work, work_bytes, result, 16);
-	const void *ins[2] = { in, in2 };
-	const uint64_t ins_bytes[2] = { in_bytes, in2_bytes };
-	for (int i = 0; i < 2; i++)
-		hit = hit || mdm_ranges_intersect(out, out_room, ins[i], ins_bytes[i]) || mdm_ranges_intersect(work, work_bytes, ins[i], ins_bytes[i]) ||
-		      mdm_ranges_intersect(result, 16, ins[i], ins_bytes[i]);
-	if (hit) REFUSE("%s: the output, the workspace, the result and the input intersect", who);
 	return MDEMOD_OK;
 }
 
@@ -558,8 +510,8 @@ try { MDEMOD_API_ENTER
 	int rc = png_check_picture(who, width, height, planes, filter, segment);
 	if (rc) return rc;
 	const uint64_t area = static_cast<uint64_t>(width) * height;
-	if ((rc = check_buffers(who, picture_dev, area * planes, 1, valid_dev, area, out_dev, out_room, result_dev, work_dev, work_bytes,
-	                        mdemod_png_workspace(width, height, planes, valid_dev != nullptr, segment))))
+	if ((rc = enc_check_buffers(who, "bytes", picture_dev, area * planes, 1, valid_dev, area, out_dev, out_room, result_dev, work_dev, work_bytes,
+	                            mdemod_png_workspace(width, height, planes, valid_dev != nullptr, segment))))
 		return rc;
 	if ((rc = mdm_select_device(device))) return rc;
 	return encode_run(picture_dev, valid_dev, width, height, planes, filter, segment, out_dev, out_room, result_dev, work_dev, static_cast<hipStream_t>(hip_stream));
@@ -572,7 +524,7 @@ try { MDEMOD_API_ENTER
 	const char *who = "mdemod_png_deflate_device";
 	int rc = png_check_bytes(who, n_bytes, segment);
 	if (rc) return rc;
-	if ((rc = check_buffers(who, bytes_dev, n_bytes, 16, nullptr, 0, out_dev, out_room, result_dev, work_dev, work_bytes, mdemod_png_deflate_workspace(n_bytes, segment))))
+	if ((rc = enc_check_buffers(who, "bytes", bytes_dev, n_bytes, 16, nullptr, 0, out_dev, out_room, result_dev, work_dev, work_bytes, mdemod_png_deflate_workspace(n_bytes, segment))))
 		return rc;
 	if ((rc = mdm_select_device(device))) return rc;
 	const uint32_t sb = png_segment_bytes(segment);
@@ -583,18 +535,7 @@ try { MDEMOD_API_ENTER
 int
 mdemod_png_result(const uint64_t *result_dev, uint64_t *bytes, int device, void *hip_stream)
 try { MDEMOD_API_ENTER
-	if (!result_dev) REFUSE("mdemod_png_result: the result is needed");
-	int rc = mdm_select_device(device);
-	if (rc) return rc;
-	uint64_t r[2] = { 0, 0 };
-	HIP_TRY(hipMemcpyAsync(r, result_dev, sizeof r, hipMemcpyDeviceToHost, static_cast<hipStream_t>(hip_stream)));
-	HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(hip_stream)));
-	if (bytes) *bytes = r[0];
-	if (!r[1]) {
-		mdm_note_error("mdemod_png_result: the output needs %llu bytes and out_room was less; nothing was written", static_cast<unsigned long long>(r[0]));
-		return MDEMOD_ERR_OVERFLOW;
-	}
-	return MDEMOD_OK;
+	return enc_result("mdemod_png_result", result_dev, bytes, device, hip_stream);
 } MDEMOD_API_CATCH
 
 int
@@ -624,12 +565,7 @@ try { MDEMOD_API_ENTER
 	HIP_TRY(hipMemcpyAsync(r, d_result, sizeof r, hipMemcpyDeviceToHost, nullptr));
 	HIP_TRY(hipStreamSynchronize(nullptr));
 	if (!r[1]) { mdm_note_error("%s: the file of %llu bytes passed its bound of %llu", who, static_cast<unsigned long long>(r[0]), static_cast<unsigned long long>(room)); return MDEMOD_ERR_OVERFLOW; }
-	uint8_t *host = static_cast<uint8_t *>(malloc(r[0]));
-	if (!host) { mdm_note_error("%s: no memory for a file of %llu bytes", who, static_cast<unsigned long long>(r[0])); return MDEMOD_ERR_NOMEM; }
-	const hipError_t e = hipMemcpy(host, d_out, r[0], hipMemcpyDeviceToHost);
-	if (e != hipSuccess) { free(host); HIP_TRY(e); }
-	*file = host; *bytes = r[0];
-	return MDEMOD_OK;
+	return enc_download(who, d_out, r[0], file, bytes);
 } MDEMOD_API_CATCH
 
 } /* extern "C" */

@@ -9,9 +9,7 @@
 #include <vector>
 
 #include "png_host.h"
-#include "mdemod_internal_api.h"
-
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
+#include "encoder_host.h"
 
 namespace {
 
@@ -177,18 +175,6 @@ model_filter(const uint8_t *picture, const uint8_t *valid, uint32_t width, uint3
 	}
 }
 
-int
-give(const char *who, const std::vector<uint8_t> &file, uint8_t *out, uint64_t out_room, uint64_t *bytes)
-{
-	if (bytes) *bytes = file.size();
-	if (file.size() > out_room) {
-		mdm_note_error("%s: the output needs %llu bytes, out_room is %llu", who, static_cast<unsigned long long>(file.size()), static_cast<unsigned long long>(out_room));
-		return MDEMOD_ERR_OVERFLOW;
-	}
-	if (!file.empty()) memcpy(out, file.data(), file.size());
-	return MDEMOD_OK;
-}
-
 } /* namespace */
 
 int
@@ -283,7 +269,7 @@ try { MDEMOD_API_ENTER
 	std::vector<uint8_t> file;
 	const uint64_t s = model_chunks(bytes, n_bytes, png_segment_bytes(segment), file);
 	if (stored) *stored = s;
-	return give(who, file, out, out_room, bytes_out);
+	return enc_give(who, file, out, out_room, bytes_out);
 } MDEMOD_API_CATCH
 
 int
@@ -305,7 +291,7 @@ try { MDEMOD_API_ENTER
 	uint8_t adler[4] = { static_cast<uint8_t>(b >> 8), static_cast<uint8_t>(b), static_cast<uint8_t>(a >> 8), static_cast<uint8_t>(a) };
 	chunk(file, "IDAT", adler, 4);
 	chunk(file, "IEND", nullptr, 0);
-	return give(who, file, out, out_room, bytes_out);
+	return enc_give(who, file, out, out_room, bytes_out);
 } MDEMOD_API_CATCH
 
 } /* extern "C" */

@@ -19,7 +19,6 @@
 #define PNG_HD inline
 #endif
 
-#define PNG_SCAN_THREADS 1024                   /* segments that one pass of the offset scan holds */
 #define PNG_LL        286                       /* literal/length symbols */
 #define PNG_LL_ROOM   288                       /* (the distance length stands behind the last literal/length one) */
 #define PNG_CL        19

@@ -129,8 +129,6 @@ polar_nodes(PolarNodesArgs a)
 
 namespace {
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 uint64_t
 table_bytes(const mdemod_polar_solver &s)
 {
@@ -234,12 +232,10 @@ try { MDEMOD_API_ENTER
 		if (!nodes_dev[k]) REFUSE("%s: the node buffer of pass %u is needed", who, k);
 		if (reinterpret_cast<uintptr_t>(nodes_dev[k]) & 3u) REFUSE("%s: the node buffers must stand at multiples of 4 bytes", who);
 	}
-	bool hit = false;
-	for (uint32_t k = 0; k < n; k++) {
-		hit = hit || mdm_ranges_intersect(nodes_dev[k], node_bytes, work_dev, need);
-		for (uint32_t j = 0; j < k; j++) hit = hit || mdm_ranges_intersect(nodes_dev[k], node_bytes, nodes_dev[j], node_bytes);
-	}
-	if (hit) REFUSE("%s: the node buffers and the work buffer intersect", who);
+	MdmBuffers b;
+	b.out(work_dev, need);
+	for (uint32_t k = 0; k < n; k++) b.out(nodes_dev[k], node_bytes);
+	if (!b.apart()) REFUSE("%s: the node buffers and the work buffer intersect", who);
 	if ((rc = mdm_select_device(device))) return rc;
 	return nodes_run(*frame, solvers, n, nodes_dev, work_dev, static_cast<hipStream_t>(hip_stream));
 } MDEMOD_API_CATCH

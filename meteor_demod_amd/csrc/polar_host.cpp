@@ -16,8 +16,6 @@
 #include "polar_host.h"
 #include "mdemod_internal_api.h"
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 namespace {
 
 inline double wrap180(double d) { d = fmod(d, 360.0); return d >= 180.0 ? d - 360.0 : d < -180.0 ? d + 360.0 : d; }

@@ -1818,8 +1818,6 @@ try { MDEMOD_API_ENTER
 
 /* ---- test entries (mdemod_internal_api.h): the production launches above on tables a test makes up -------------------------- */
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 extern "C" int
 mdemod_selftest_seam_match(int mode, const int8_t *a_dev, uint64_t a_symbols, const int8_t *b_dev, uint64_t b_symbols,
                            const uint64_t *a_off, const uint32_t *a_cnt, const uint64_t *b_off, const uint32_t *b_cnt,
@@ -1891,4 +1889,3 @@ try { MDEMOD_API_ENTER
 	HIP_TRY(hipStreamSynchronize(st));
 	return MDEMOD_OK;
 } MDEMOD_API_CATCH
-#undef REFUSE

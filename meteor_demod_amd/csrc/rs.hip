@@ -198,8 +198,6 @@ rs_decode(const uint32_t *cadu, uint32_t *vcdu, uint32_t *info, uint32_t derando
 
 namespace {
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 int
 rs_run(const mdemod_rs_opts &o, const uint8_t *cadu_dev, uint64_t n, uint8_t *vcdu_dev, mdemod_rs_info *info_dev, hipStream_t st)
 {
@@ -228,8 +226,7 @@ try { MDEMOD_API_ENTER
 		REFUSE("mdemod_rs_decode_device: the CADUs, the VCDUs and the report must stand at multiples of 4 bytes");
 	if (n > 0x7FFFFFFFull) REFUSE("rs: %llu frames are more than one launch takes", (unsigned long long)n);
 	const uint64_t in_bytes = n * MDEMOD_RS_CADU_BYTES, out_bytes = n * MDEMOD_RS_VCDU_BYTES, info_bytes = n * sizeof(mdemod_rs_info);
-	if (mdm_ranges_intersect(cadu_dev, in_bytes, vcdu_dev, out_bytes) || mdm_ranges_intersect(cadu_dev, in_bytes, info_dev, info_bytes) ||
-	    mdm_ranges_intersect(vcdu_dev, out_bytes, info_dev, info_bytes))
+	if (!MdmBuffers().in(cadu_dev, in_bytes).out(vcdu_dev, out_bytes).out(info_dev, info_bytes).apart())
 		REFUSE("mdemod_rs_decode_device: the CADUs, the VCDUs and the report intersect (the blocks of one launch would read what others write)");
 	rc = mdm_select_device(device);
 	if (rc) return rc;

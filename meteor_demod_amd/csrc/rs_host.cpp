@@ -8,8 +8,6 @@
 #include "rs_host.h"
 #include "mdemod_internal_api.h"
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 namespace {
 
 constexpr RsTables TAB = rs_make_tables();

@@ -7,21 +7,13 @@
 #include <cstring>
 #include <vector>
 
+#include "buffers.h"
 #include "mdemod_internal_api.h"
 #include "sun_host.h"
-
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
 
 namespace {
 
 constexpr double SUN_PI = 3.14159265358979323846, SUN_RAD = SUN_PI / 180.0;
-
-bool
-intersect(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-	return a && b && a_bytes && b_bytes && x < y + b_bytes && y < x + a_bytes;
-}
 
 /* the Earth-fixed unit vector to the sun */
 void
@@ -87,14 +79,14 @@ sun_check_apply(const char *who, const uint8_t *const image[3], uint8_t *const o
 		low |= reinterpret_cast<uintptr_t>(image[k]) | reinterpret_cast<uintptr_t>(out[k]);
 	}
 	if (low & 3u) REFUSE("%s: the pictures, the outputs, the gain table and the workspace must stand at multiples of 4 bytes", who);
-	bool hit = has_work && intersect(gain, table, work, need);
+	bool hit = has_work && mdm_ranges_intersect(gain, table, work, need);
 	for (int k = 0; k < 3; k++) {
 		if (!(slot_mask >> k & 1u)) continue;
-		hit = hit || intersect(out[k], area, gain, table) || (has_work && (intersect(out[k], area, work, need) || intersect(image[k], area, work, need)));
+		hit = hit || mdm_ranges_intersect(out[k], area, gain, table) || (has_work && (mdm_ranges_intersect(out[k], area, work, need) || mdm_ranges_intersect(image[k], area, work, need)));
 		for (int j = 0; j < 3; j++) {
 			if (!(slot_mask >> j & 1u)) continue;
-			if (j != k) hit = hit || intersect(out[k], area, out[j], area);
-			if (j != k || out[k] != image[j]) hit = hit || intersect(out[k], area, image[j], area);
+			if (j != k) hit = hit || mdm_ranges_intersect(out[k], area, out[j], area);
+			if (j != k || out[k] != image[j]) hit = hit || mdm_ranges_intersect(out[k], area, image[j], area);
 		}
 	}
 	if (hit) REFUSE("%s: the pictures, the outputs, the gain table and the workspace intersect (only the output of a slot may be its picture itself)", who);

@@ -237,8 +237,6 @@ sv_fill_starts(uint64_t *starts, uint64_t pitch, uint64_t skip, uint32_t n)
 
 namespace {
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 struct SvGeometry {
 	int      log2n;
 	uint32_t S;                   /* segments in flight per block */

@@ -20,8 +20,6 @@ namespace {
 
 const double kPi = 3.14159265358979323846;
 
-#define REFUSE(...) do { mdm_note_error(__VA_ARGS__); return MDEMOD_ERR_PARAM; } while (0)
-
 int
 check_rates(const mdemod_params &p)
 {

@@ -10,12 +10,11 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 
-from . import _capi
-from ._capi import check, take_bytes
+from . import _capi, _encode
+from ._capi import check
 
 MAX_WIDTH, MAX_HEIGHT, MAX_RESTART, RESTART = 8192, 16384, 64, 32
 HEAD = {1: 330, 3: 613}
@@ -52,14 +51,8 @@ def lib() -> C.CDLL:
 
 def _picture(picture) -> tuple:
     """(contiguous uint8 array, width, height, planes) of a numpy picture [H, W], [H, W, 1] or [H, W, 3]."""
-    px = np.ascontiguousarray(picture, dtype=np.uint8)
-    if px.ndim == 2:
-        planes = 1
-    elif px.ndim == 3 and px.shape[2] in (1, 3):
-        planes = int(px.shape[2])
-    else:
-        raise ValueError(f"a picture is uint8 [H, W] or [H, W, 3], got {tuple(px.shape)}")
-    return px, int(px.shape[1]), int(px.shape[0]), planes
+    px, _, w, h, planes = _encode.picture(picture)
+    return px, w, h, planes
 
 
 def bound(width: int, height: int, planes: int, restart_interval: int = 0) -> int:
@@ -72,12 +65,6 @@ def workspace(width: int, height: int, planes: int, restart_interval: int = 0) -
 
 
 # ------------------------------------------------------------------------------------------------------------------ device
-def _finish(out, result, d, stream) -> bytes:
-    n = C.c_uint64()
-    check(lib().mdemod_jpeg_result(C.c_void_p(result.data_ptr()), C.byref(n), d, stream), "mdemod_jpeg_result")
-    return out[: n.value].cpu().numpy().tobytes()
-
-
 def _first_room(w: int, h: int, planes: int, restart_interval: int) -> int:
     """The output buffer ``encode_tensor`` tries first: the bound (6.5 bytes a sample), but no more than twice the picture and 1 MiB."""
     return min(max(bound(w, h, planes, restart_interval), 1), 2 * w * h * planes + (1 << 20))
@@ -87,34 +74,19 @@ def encode_tensor(picture, quality: int = 90, restart_interval: int = 0, out_roo
     """A contiguous uint8 tensor [H, W], [H, W, 1] or [H, W, 3] on the GPU into the file's bytes, on the tensor's device and the
     current stream; only the file is downloaded.  ``out_room`` (default: the bound, at most twice the picture and 1 MiB) is the
     device buffer the file must fit; a ``MdemodError`` names the bytes needed when it does not."""
-    import torch
-    if picture.dtype != torch.uint8 or not picture.is_contiguous() or not picture.is_cuda:
-        raise ValueError("the picture must be a contiguous uint8 tensor on the GPU")
-    if picture.dim() == 2:
-        planes = 1
-    elif picture.dim() == 3 and picture.shape[2] in (1, 3):
-        planes = int(picture.shape[2])
-    else:
-        raise ValueError(f"a picture is uint8 [H, W] or [H, W, 3], got {tuple(picture.shape)}")
-    h, w = int(picture.shape[0]), int(picture.shape[1])
-    dev = picture.device
-    d = dev.index or 0
-    stream = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
+    w, h, planes = _encode.tensor(picture)
     need = workspace(w, h, planes, restart_interval)
     for attempt in range(2):
         room = int(out_room) if out_room is not None else _first_room(w, h, planes, restart_interval)
-        out = torch.empty(max(room, 1), dtype=torch.uint8, device=dev)
-        work = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        result = torch.zeros(2, dtype=torch.int64, device=dev)
-        check(lib().mdemod_jpeg_encode_device(C.c_void_p(picture.data_ptr()), w, h, planes, int(quality), int(restart_interval), C.c_void_p(out.data_ptr()), room,
-                                              C.c_void_p(result.data_ptr()), C.c_void_p(work.data_ptr()), need, d, stream), "mdemod_jpeg_encode_device")
+        s = _encode.Scratch(picture, room, need)
+        check(lib().mdemod_jpeg_encode_device(C.c_void_p(picture.data_ptr()), w, h, planes, int(quality), int(restart_interval), *s.tail), "mdemod_jpeg_encode_device")
         try:
-            return _finish(out, result, d, stream)
+            return s.finish(lib().mdemod_jpeg_result, "mdemod_jpeg_result")
         except _capi.MdemodError as e:
             # a picture that codes to more than twice its size (noise at quality 100): once more with what it needs
             if out_room is not None or attempt or e.code != _capi.MDEMOD_ERR_OVERFLOW:
                 raise
-            out_room = int(result.cpu()[0])
+            out_room = int(s.result.cpu()[0])
     raise AssertionError("unreachable")
 
 
@@ -125,28 +97,17 @@ def entropy(coef, planes: int, restart_interval: int = 0, out_room: int | None =
     if coef.dtype != torch.int16 or not coef.is_contiguous() or coef.dim() != 2 or coef.shape[1] != 64 or coef.shape[0] % planes:
         raise ValueError("the coefficients must be a contiguous int16 tensor [n_mcus * planes, 64]")
     n_mcus = int(coef.shape[0]) // planes
-    dev = coef.device
-    d = dev.index or 0
-    stream = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
     room = int(out_room) if out_room is not None else int(lib().mdemod_jpeg_entropy_bound(n_mcus, planes, restart_interval))
-    need = int(lib().mdemod_jpeg_entropy_workspace(n_mcus, restart_interval))
-    out = torch.empty(max(room, 1), dtype=torch.uint8, device=dev)
-    work = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    result = torch.zeros(2, dtype=torch.int64, device=dev)
-    check(lib().mdemod_jpeg_entropy_device(C.c_void_p(coef.data_ptr()), n_mcus, planes, int(restart_interval), C.c_void_p(out.data_ptr()), room,
-                                           C.c_void_p(result.data_ptr()), C.c_void_p(work.data_ptr()), need, d, stream), "mdemod_jpeg_entropy_device")
-    return _finish(out, result, d, stream)
+    s = _encode.Scratch(coef, room, int(lib().mdemod_jpeg_entropy_workspace(n_mcus, restart_interval)))
+    check(lib().mdemod_jpeg_entropy_device(C.c_void_p(coef.data_ptr()), n_mcus, planes, int(restart_interval), *s.tail), "mdemod_jpeg_entropy_device")
+    return s.finish(lib().mdemod_jpeg_result, "mdemod_jpeg_result")
 
 
 def encode_host(picture, quality: int = 90, restart_interval: int = 0, device: int = 0) -> bytes:
     """``mdemod_jpeg_encode_host`` on a numpy picture."""
     px, w, h, planes = _picture(picture)
-    file, n = C.c_void_p(), C.c_uint64()
-    check(lib().mdemod_jpeg_encode_host(px.ctypes.data, w, h, planes, int(quality), int(restart_interval), C.byref(file), C.byref(n), int(device)), "mdemod_jpeg_encode_host")
-    try:
-        return take_bytes(file.value, n.value).tobytes()
-    finally:
-        lib().mdemod_jpeg_free(file)
+    return _encode.host_call(lib().mdemod_jpeg_encode_host, "mdemod_jpeg_encode_host", lib().mdemod_jpeg_free,
+                             (px.ctypes.data, w, h, planes, int(quality), int(restart_interval)), device)
 
 
 def encode(picture, quality: int = 90, restart_interval: int = 0, device: int = 0) -> bytes:
@@ -158,10 +119,7 @@ def encode(picture, quality: int = 90, restart_interval: int = 0, device: int = 
 
 def write(path, picture, quality: int = 90, restart_interval: int = 0, device: int = 0) -> int:
     """``encode`` into the file ``path``; returns the bytes written."""
-    data = encode(picture, quality, restart_interval, device)
-    with open(os.fspath(path), "wb") as f:
-        f.write(data)
-    return len(data)
+    return _encode.write(path, encode(picture, quality, restart_interval, device))
 
 
 # ------------------------------------------------------------------------------------------------------------- the host model

@@ -18,8 +18,9 @@ import os
 
 import numpy as np
 
-from . import _capi
-from ._capi import check, take_bytes
+from . import _capi, _encode
+from ._capi import check
+from ._encode import picture as _picture
 
 MAX_WIDTH, MAX_HEIGHT, MAX_SEGMENT, FILTER_ADAPT = 8192, 16384, 32, 5
 HEAD, TAIL, SEGMENT_OVERHEAD = 47, 28, 17
@@ -53,23 +54,6 @@ def lib() -> C.CDLL:
     return _capi.bind(SIGNATURES, MODEL_SIGNATURES)
 
 
-def _picture(picture, valid=None) -> tuple:
-    """(contiguous uint8 picture, contiguous uint8 mask or None, width, height, planes) of numpy arrays."""
-    px = np.ascontiguousarray(picture, dtype=np.uint8)
-    if px.ndim == 2:
-        planes = 1
-    elif px.ndim == 3 and px.shape[2] in (1, 3):
-        planes = int(px.shape[2])
-    else:
-        raise ValueError(f"a picture is uint8 [H, W] or [H, W, 3], got {tuple(px.shape)}")
-    va = None
-    if valid is not None:
-        va = np.ascontiguousarray(valid, dtype=np.uint8)
-        if va.shape != px.shape[:2]:
-            raise ValueError(f"the mask of a picture {tuple(px.shape)} is uint8 [H, W], got {tuple(va.shape)}")
-    return px, va, int(px.shape[1]), int(px.shape[0]), planes
-
-
 def _ptr(a):
     return a.ctypes.data if a is not None else None
 
@@ -92,40 +76,20 @@ def deflate_bound(n_bytes: int, segment: int = 0) -> int:
 
 
 # ------------------------------------------------------------------------------------------------------------------ device
-def _finish(out, result, d, stream) -> bytes:
-    n = C.c_uint64()
-    check(lib().mdemod_png_result(C.c_void_p(result.data_ptr()), C.byref(n), d, stream), "mdemod_png_result")
-    return out[: n.value].cpu().numpy().tobytes()
-
-
 def encode_tensor(picture, valid=None, filter: int = FILTER_ADAPT, segment: int = 0, out_room: int | None = None) -> bytes:
     """A contiguous uint8 tensor [H, W], [H, W, 1] or [H, W, 3] on the GPU (and a mask [H, W] on the same device, or None) into the
     file's bytes, on the tensor's device and the current stream; only the file is downloaded.  ``out_room`` (default: the bound) is
     the device buffer the file must fit; a ``MdemodError`` names the bytes needed when it does not."""
     import torch
-    if picture.dtype != torch.uint8 or not picture.is_contiguous() or not picture.is_cuda:
-        raise ValueError("the picture must be a contiguous uint8 tensor on the GPU")
-    if picture.dim() == 2:
-        planes = 1
-    elif picture.dim() == 3 and picture.shape[2] in (1, 3):
-        planes = int(picture.shape[2])
-    else:
-        raise ValueError(f"a picture is uint8 [H, W] or [H, W, 3], got {tuple(picture.shape)}")
-    h, w = int(picture.shape[0]), int(picture.shape[1])
+    w, h, planes = _encode.tensor(picture)
     if valid is not None and (valid.dtype != torch.uint8 or not valid.is_contiguous() or valid.device != picture.device or tuple(valid.shape) != (h, w)):
         raise ValueError("the mask must be a contiguous uint8 tensor [H, W] on the picture's device")
-    dev = picture.device
-    d = dev.index or 0
-    stream = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
     need = workspace(w, h, planes, valid is not None, segment)
     room = int(out_room) if out_room is not None else bound(w, h, planes, valid is not None, segment)
-    out = torch.empty(max(room, 1), dtype=torch.uint8, device=dev)
-    work = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    result = torch.zeros(2, dtype=torch.int64, device=dev)
+    s = _encode.Scratch(picture, room, need)
     check(lib().mdemod_png_encode_device(C.c_void_p(picture.data_ptr()), C.c_void_p(valid.data_ptr()) if valid is not None else None, w, h, planes, int(filter),
-                                         int(segment), C.c_void_p(out.data_ptr()), room, C.c_void_p(result.data_ptr()), C.c_void_p(work.data_ptr()), need, d, stream),
-          "mdemod_png_encode_device")
-    return _finish(out, result, d, stream)
+                                         int(segment), *s.tail), "mdemod_png_encode_device")
+    return s.finish(lib().mdemod_png_result, "mdemod_png_result")
 
 
 def deflate(data, segment: int = 0, out_room: int | None = None) -> bytes:
@@ -134,28 +98,17 @@ def deflate(data, segment: int = 0, out_room: int | None = None) -> bytes:
     if data.dtype != torch.uint8 or not data.is_contiguous() or not data.is_cuda or data.dim() != 1:
         raise ValueError("the bytes must be a contiguous one-dimensional uint8 tensor on the GPU")
     n = int(data.shape[0])
-    dev = data.device
-    d = dev.index or 0
-    stream = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
     room = int(out_room) if out_room is not None else deflate_bound(n, segment)
-    need = int(lib().mdemod_png_deflate_workspace(n, segment))
-    out = torch.empty(max(room, 1), dtype=torch.uint8, device=dev)
-    work = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    result = torch.zeros(2, dtype=torch.int64, device=dev)
-    check(lib().mdemod_png_deflate_device(C.c_void_p(data.data_ptr()), n, int(segment), C.c_void_p(out.data_ptr()), room, C.c_void_p(result.data_ptr()),
-                                          C.c_void_p(work.data_ptr()), need, d, stream), "mdemod_png_deflate_device")
-    return _finish(out, result, d, stream)
+    s = _encode.Scratch(data, room, int(lib().mdemod_png_deflate_workspace(n, segment)))
+    check(lib().mdemod_png_deflate_device(C.c_void_p(data.data_ptr()), n, int(segment), *s.tail), "mdemod_png_deflate_device")
+    return s.finish(lib().mdemod_png_result, "mdemod_png_result")
 
 
 def encode_host(picture, valid=None, filter: int = FILTER_ADAPT, segment: int = 0, device: int = 0) -> bytes:
     """``mdemod_png_encode_host`` on numpy arrays."""
     px, va, w, h, planes = _picture(picture, valid)
-    file, n = C.c_void_p(), C.c_uint64()
-    check(lib().mdemod_png_encode_host(px.ctypes.data, _ptr(va), w, h, planes, int(filter), int(segment), C.byref(file), C.byref(n), int(device)), "mdemod_png_encode_host")
-    try:
-        return take_bytes(file.value, n.value).tobytes()
-    finally:
-        lib().mdemod_png_free(file)
+    return _encode.host_call(lib().mdemod_png_encode_host, "mdemod_png_encode_host", lib().mdemod_png_free,
+                             (px.ctypes.data, _ptr(va), w, h, planes, int(filter), int(segment)), device)
 
 
 def encode(picture, valid=None, filter: int = FILTER_ADAPT, segment: int = 0, device: int = 0) -> bytes:
@@ -168,10 +121,7 @@ def encode(picture, valid=None, filter: int = FILTER_ADAPT, segment: int = 0, de
 
 def write(path, picture, valid=None, filter: int = FILTER_ADAPT, segment: int = 0, device: int = 0) -> int:
     """``encode`` into the file ``path``; returns the bytes written."""
-    data = encode(picture, valid, filter, segment, device)
-    with open(os.fspath(path), "wb") as f:
-        f.write(data)
-    return len(data)
+    return _encode.write(path, encode(picture, valid, filter, segment, device))
 
 
 # ------------------------------------------------------------------------------------------------------------- the host model

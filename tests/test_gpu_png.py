@@ -32,7 +32,7 @@ def _dev(a, gpu_device):
 
 def _scan_threads() -> int:
     """The segments one pass of the offset scan holds: the scan kernel's own constant."""
-    return int(re.search(r"#define PNG_SCAN_THREADS\s+(\d+)", (ROOT / "meteor_demod_amd" / "csrc" / "png_host.h").read_text()).group(1))
+    return int(re.search(r"#define ENC_SCAN_THREADS\s+(\d+)", (ROOT / "meteor_demod_amd" / "csrc" / "encoder_device.h").read_text()).group(1))
 
 
 # ------------------------------------------------------------------------------------------------------ file against model
