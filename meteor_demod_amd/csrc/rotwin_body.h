@@ -25,6 +25,7 @@
 #include "demod_internal.h"
 #include "demod_device.h"
 #include "clock_jump.h"
+#include "rot_firing_index.h"
 
 #pragma clang fp contract(off)
 
@@ -93,7 +94,12 @@ blind_steps(float p, float f)
  * behind the four checked steps depends on two small integers: isub (< -O) and j, the number of the first three checked steps that
  * stayed below the threshold.  One 16-byte LDS read at isub * 4 + j replaces the division by -O, the two carries and the bank
  * arithmetic (24 VALU instructions of a firing, with an LDS pipe that is idle: profiles/r07_clock_table.md).
- * An entry is { samples to advance, fire_sub (filter.c:52's `interp_idx`, host tests only), isub, bank }. */
+ * An entry is { samples to advance, fire_sub (filter.c:52's `interp_idx`, host tests only), isub, bank }.
+ * Every clock but the closed-form one of configs[3] (KS 109, never a table) carries isub as the byte offset of its four entries,
+ * isub << ROT_CLOCK_ROW_SHIFT, and the LDS copy of the table holds it that way: the entry's address is one addition of a select
+ * cascade on the masks that pick the phase (rot_firing_index.h; the shift, three selects of 16 / 0 and two three-way additions
+ * before round 11). */
+template <int KS> struct RotIsub { enum { SHIFT = KS == 109 ? 0 : ROT_CLOCK_ROW_SHIFT, ONE = 1 << SHIFT }; };
 typedef int rot_i4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) rot_i4 *rot_clktab_t;
 struct RotClockConsts { int k_safe, steps_need, interp; float f_hi; uint32_t magic; float inv; const cj_sched *jump; rot_clktab_t tab; };   /* jump: the launch arguments' two schedules, read where they are used (scalar loads) rather than held in registers; tab: null = this context keeps the arithmetic */
@@ -134,19 +140,20 @@ rot_clock_fast(const RotClockConsts &K, float thr, int v_end, int v_fast_end, fl
 		t_phase = ph;
 		/* the instances with compiled-in blind steps always have the table (the launcher checks it); the generic one asks (wave-uniform) */
 		if ((KS == 14 || KS == 6) || (KS == 0 && K.tab)) {
-			const uint32_t off = ((uint32_t)isub << 6) + (c1 ? 0u : 16u) + (c2 ? 0u : 16u) + (c3 ? 0u : 16u);      /* entry isub * 4 + j */
+			const uint32_t off = (uint32_t)isub + rot_clock_sel(c1, c2, c3);      /* entry isub * 4 + j */
 			const rot_i4 e = *reinterpret_cast<rot_clktab_t>(reinterpret_cast<const __attribute__((address_space(3))) unsigned char *>(K.tab) + off);
 			v_cur += e.x;
 			isub = e.z;
 			bank = e.w;
 		} else {
-			const uint32_t w = (uint32_t)(isub + k_safe + 1 + (c1 ? 0 : 1) + (c2 ? 0 : 1) + (c3 ? 0 : 1));
+			const int isub_old = isub >> RotIsub<KS>::SHIFT;
+			const uint32_t w = (uint32_t)(isub_old + k_safe + 1 + (c1 ? 0 : 1) + (c2 ? 0 : 1) + (c3 ? 0 : 1));
 			const uint32_t q = (interp == 1) ? w : __umulhi(w, K.magic);     /* floor(w / interp); the magic of 1 does not fit 32 bits */
 			const int isub_new = (int)(w - q * (uint32_t)interp);
-			v_cur += (int)q + (isub_new > 0 ? 1 : 0) - (isub > 0 ? 1 : 0);   /* samples pushed: ceil(w/interp) - (isub>0) */
+			v_cur += (int)q + (isub_new > 0 ? 1 : 0) - (isub_old > 0 ? 1 : 0);   /* samples pushed: ceil(w/interp) - (isub>0) */
 			const int fire_sub = (isub_new == 0) ? interp - 1 : isub_new - 1;
 			bank = interp - 1 - fire_sub;                                    /* filter.c:52 */
-			isub = isub_new;
+			isub = isub_new << RotIsub<KS>::SHIFT;
 		}
 		fired = c4;
 	}
@@ -208,7 +215,11 @@ rotwin_demod(const DemodLaunch &L)
 	if (threadIdx.x < 32) lut[threadIdx.x] = L.tanh_lut[threadIdx.x];
 	const bool has_clktab = KS != 109 && C.clock_tab != nullptr;               /* (wave-uniform: a launch argument) */
 	if (has_clktab)
-		for (int i = (int)threadIdx.x; i < 4 * C.interp; i += (int)blockDim.x) clktab[i] = reinterpret_cast<const rot_i4 *>(C.clock_tab)[i];
+		for (int i = (int)threadIdx.x; i < 4 * C.interp; i += (int)blockDim.x) {
+			rot_i4 e = reinterpret_cast<const rot_i4 *>(C.clock_tab)[i];
+			e.z = rot_clock_entry_scaled(e.z);                 /* (the clock carries isub as a byte offset: rot_clock_fast) */
+			clktab[i] = e;
+		}
 
 	int n = 0;
 	const sample_t *src = nullptr;
@@ -233,6 +244,12 @@ rotwin_demod(const DemodLaunch &L)
 	auto st_flags = [&](int v) { if (RS & 4) r_flags = v; else sli[S_FLAGS * 64] = v; };
 	auto ld_lastv = [&]() -> int { return (RS & 8) ? r_lastv : sli[S_LASTV * 64]; };
 	auto st_lastv = [&](int v) { if (RS & 8) r_lastv = v; else sli[S_LASTV * 64] = v; };
+	/* The symbols of this call are counted by the ring: sym_base, those before the ring's current run (a multiple of RING, touched
+	 * once per RING symbols), plus the place of ring_off in the run.  A policy that keeps lastv in a register leaves its slot idle:
+	 * sym_base lives there and the loop holds no symbol counter at all; the others keep it in a register. */
+	uint32_t r_symbase = 0;
+	auto ld_symbase = [&]() -> uint32_t { return (RS & 8) ? (uint32_t)sli[S_LASTV * 64] : r_symbase; };
+	auto st_symbase = [&](uint32_t v) { if (RS & 8) sli[S_LASTV * 64] = (int)v; else r_symbase = v; };
 	{
 		float err = 1000.0f, t_prev = 0.0f, inph = 0.0f;
 		int fl = MDEMOD_FLAG_UPDOWN_POS | (1 << MDEMOD_FLAG_DUAL_SHIFT);
@@ -248,6 +265,7 @@ rotwin_demod(const DemodLaunch &L)
 		st_flags(fl & 7);
 		st_tprev(t_prev); sl[S_INPHASE * 64] = inph;
 		sli[S_EVCALL * 64] = 0; sli[S_FIRSTLOCK * 64] = -1; st_lastv(-1);
+		st_symbase(0);
 	}
 
 	/* ---- window: the first kBack slots = history ([stream][kBack] float pairs), the rest = the first granules of the block ---- */
@@ -284,7 +302,8 @@ rotwin_demod(const DemodLaunch &L)
 	/* (a policy whose slide keeps rot and base as scalars: their first value is a scalar definition too - a plain 0 is the zero the
 	 * compiler already has in a VGPR, and one vector input makes both loop phis vector registers) */
 	if constexpr (W::SCALAR_SLIDE) asm("s_mov_b32 %0, 0\n\ts_mov_b32 %1, 0" : "=s"(rot), "=s"(base));
-	int isub = 0, bank = interp - 1;                       /* bank: filter.c:52's `interp - 1 - interp_idx` of the pending firing */
+	int isub = 0, bank = interp - 1;                       /* isub: scaled (RotIsub<KS>); bank: filter.c:52's `interp - 1 - interp_idx` of the pending firing */
+	constexpr int ISH = RotIsub<KS>::SHIFT, IONE = RotIsub<KS>::ONE;
 	bool fired = false;
 	bool done = !valid || n == 0;
 	/* A lane that is done parks its sample position past everything: the loop's votes are then comparisons of v_cur alone, whose
@@ -292,7 +311,10 @@ rotwin_demod(const DemodLaunch &L)
 	 * two of them per iteration until round 7) */
 	constexpr int V_DONE = 0x3FFFFFFF;
 	int v_cur = done ? V_DONE : kBack - 1;
-	uint32_t sym_call = 0;
+	/* where the next symbol goes in the lane's ring, stepped per symbol (rot_firing_index.h), and with it the count of symbols */
+	static_assert(rot_ring_geometry_ok(RING, BLOCK), "output ring: the offset's two fields");
+	uint32_t ring_off = 0;
+	auto sym_count = [&]() -> uint32_t { return ld_symbase() + rot_ring_count(ring_off, BLOCK); };
 	RotClockConsts K;
 	K.k_safe = C.step_safe; K.f_hi = C.step_fmax; K.magic = C.interp_magic; K.interp = C.interp; K.inv = C.step_inv;
 	K.steps_need = ((KS == 109 ? CJ109_MAX_STEPS : C.step_safe) + 4 + C.interp - 1) / C.interp;      /* samples that hold k_safe + 4 steps */
@@ -333,8 +355,8 @@ rotwin_demod(const DemodLaunch &L)
 					v_cur++;
 				}
 				t_phase = t_phase + t_freq;
-				bank = interp - 1 - isub;
-				isub = (isub + 1 == interp) ? 0 : isub + 1;
+				bank = interp - 1 - (isub >> ISH);
+				isub = (isub + IONE == (interp << ISH)) ? 0 : isub + IONE;
 				if (t_phase >= thr) fired = true;
 			}
 		}
@@ -423,8 +445,18 @@ rotwin_demod(const DemodLaunch &L)
 			if (emit) {
 				/* demod.c:33-47: only the LAST symbol fired inside one input sample survives (found by fuzzing in round 2: NOTEBOOK.md 5.0) */
 				const bool again = (v_cur == ld_lastv());
-				st_lastv(v_cur);
-				if (__builtin_expect(md_any(again), 0)) { if (again) sym_call--; }
+				/* (in a register the word is copied HERE, behind the compiler's back: left to the loop's phi the copy comes after the
+				 * clock, which then has to advance a second version of v_cur - two more copies round the loop) */
+				int lastv = v_cur;
+				if constexpr ((RS & 8) != 0) asm("" : "+v"(lastv));
+				st_lastv(lastv);
+				if (__builtin_expect(md_any(again), 0)) {
+					if (again) {                       /* (never the first symbol of a call: lastv starts at -1) */
+						const uint32_t prev = sym_count() - 1u;
+						st_symbase(prev & ~(uint32_t)(RING - 1));
+						ring_off = rot_ring_off(prev, RING, BLOCK);
+					}
+				}
 				float t_prev = ld_tprev();
 				md_timing_update(t_phase, t_freq, t_prev, k_t_alpha, k_t_beta, k_t_center, C.t_maxdev, out_im);
 				st_tprev(t_prev);
@@ -441,21 +473,27 @@ rotwin_demod(const DemodLaunch &L)
 				uint32_t first = 0;
 				const uint32_t changed = md_pll_update_packed<false, W::LOCK_EARLY_OUT>(pll,fl, lut, k_pll_alpha, k_pll_beta, C.pll_fmax, out_re, out_im, first);
 				if (__builtin_expect(changed != 0, 0)) {          /* a plain divergent branch: skipped when no lane of the wave takes it */
-					if (first) sli[S_FIRSTLOCK * 64] = (int)sym_call;
+					const uint32_t sym_now = sym_count();
+					if (first) sli[S_FIRSTLOCK * 64] = (int)sym_now;
 					const int ev_call = sli[S_EVCALL * 64];
 					if (ev_call < MDEMOD_MAX_LOCK_EVENTS) {
 						mdemod_lock_event ev;
-						ev.symbol = L.st.n_symbols[stream] + sym_call; ev.locked = (int)(fl & 1u); ev.pad = 0;
+						ev.symbol = L.st.n_symbols[stream] + sym_now; ev.locked = (int)(fl & 1u); ev.pad = 0;
 						L.st.events[(size_t)stream * MDEMOD_MAX_LOCK_EVENTS + ev_call] = ev;
 					}
 					sli[S_EVCALL * 64] = ev_call + 1;
 				}
 				const uint32_t sym = (uint32_t)(md_quantise(out_re) & 0xFF) | ((uint32_t)(md_quantise(out_im) & 0xFF) << 8);
 				/* RING-symbol ring per lane in LDS, [16-byte group][thread]; every RING symbols one full run (64 bytes for 32) goes out */
-				const uint32_t k = sym_call & (uint32_t)(RING - 1);
-				reinterpret_cast<uint16_t *>(stage + (k >> 3) * BLOCK)[k & 7u] = (uint16_t)sym;
-				sym_call++;
-				if (__builtin_expect((sym_call & (uint32_t)(RING - 1)) == 0, 0)) {
+				*reinterpret_cast<uint16_t *>(reinterpret_cast<unsigned char *>(stage) + ring_off) = (uint16_t)sym;
+				ring_off = rot_ring_step(ring_off, RING, BLOCK);
+				/* (the AGC's new gain and the loop's error are finished in front of the flush's branch, not behind it: their double
+				 * temporaries are dead inside the flush, whose 16-byte group then finds four registers in a row among the firing's
+				 * own - left behind the branch, the configs[1] instances took them from above everything else they use) */
+				asm volatile("" : "+v"(r_gain), "+v"(pll.err));
+				if (__builtin_expect(ring_off == 0, 0)) {                   /* the run is full */
+					const uint32_t sym_call = ld_symbase() + (uint32_t)RING;
+					st_symbase(sym_call);
 					int8_t *soft_out = L.soft + (size_t)stream * L.soft_stride * 2;
 					if (__builtin_expect(sym_call <= L.soft_cap, 1)) {
 						/* one 16-byte group in flight at a time: four would not fit next to the live registers of the wide geometry
@@ -501,7 +539,7 @@ rotwin_demod(const DemodLaunch &L)
 
 	/* ---- flush the ring ---- */
 	if (valid) {
-		const uint32_t r = sym_call & (uint32_t)(RING - 1), sb = sym_call - r;
+		const uint32_t r = rot_ring_count(ring_off, BLOCK), sb = ld_symbase();
 		for (uint32_t g = 0; g < (r >> 3); g++) {
 			if (sb + 8 * g + 8 <= L.soft_cap) { const uint4 qv = stage[g * BLOCK]; __builtin_memcpy(soft_e + 2 * (size_t)(sb + 8 * g), &qv, 16); }
 			else for (uint32_t i = 0; i < 8; i++) {
@@ -526,6 +564,7 @@ rotwin_demod(const DemodLaunch &L)
 		const uint64_t nsym0 = L.st.n_symbols[stream_e];
 		const int first_lock_call = sli[S_FIRSTLOCK * 64];
 		L.st.n_samples[stream_e] += (uint64_t)n;
+		const uint32_t sym_call = sym_count();
 		L.st.n_symbols[stream_e] = nsym0 + sym_call;
 		if (first_lock_call >= 0) L.st.first_lock[stream_e] = (int64_t)(nsym0 + (uint32_t)first_lock_call);
 		L.st.sym_this_call[stream_e] = sym_call;
