@@ -223,6 +223,27 @@ md_cabsf_short(float re, float im, uint32_t *fallbacks = nullptr)
 	return r;
 }
 
+/* The same without the branch: the short root's float, and `fallback` = the mask of the lanes that have to take md_cabsf_exact of the
+ * same pair instead (the two comparisons' own masks, OR-ed on the scalar unit: a bool made of both goes back through the vector unit
+ * when it is voted on, see md_lane_select).  For a caller that has other rare events to vote on (the rotating-window body's one rare
+ * branch, rotwin_body.h): it ORs this one in and repairs out of line.  (Written out beside md_cabsf_short, which its users keep as
+ * it was.) */
+__device__ __forceinline__ float
+md_cabsf_short_try(float re, float im, uint64_t &fallback)
+{
+	const double s = (double)re * (double)re + (double)im * (double)im;
+	const double y = __builtin_amdgcn_rsq(s);
+	const double g = s * y, h = 0.5 * y;
+	const double d = __builtin_fma(-g, g, s);
+	const double g1 = __builtin_fma(d, h, g);
+	const uint64_t gb = __builtin_bit_cast(uint64_t, g1), sb = __builtin_bit_cast(uint64_t, s);
+	const uint32_t drop = (uint32_t)gb & 0x1FFFFFFFu;
+	const bool near = (uint32_t)(drop - (0x10000000u - 0x1000u)) < 0x2000u;
+	const bool odd = (uint32_t)((uint32_t)(sb >> 32) - ((1023u - 200u) << 20)) >= (400u << 20);
+	fallback = __builtin_amdgcn_ballot_w64(near) | __builtin_amdgcn_ballot_w64(odd);
+	return (float)g1;
+}
+
 /* dsp/agc.c:13-20: bias tracking and scaling (what the rest of the symbol needs) */
 __device__ __forceinline__ cf32
 md_agc_apply(cf32 x, float gain, float &bias_re, float &bias_im)
@@ -245,6 +266,14 @@ md_agc_gain(cf32 scaled, float &gain)
 	const float mag = SHORT ? md_cabsf_short(scaled.re, scaled.im) : md_cabsf(scaled.re, scaled.im);
 	gain = gain + 0.0001f * (190.0f - mag);
 	gain = (0.0f > gain) ? 0.0f : gain;
+}
+
+/* dsp/agc.c:22-24 alone, for a caller that has the magnitude already (rotwin_body.h: the rare-path policy) */
+__device__ __forceinline__ float
+md_agc_gain_step(float gain, float mag)
+{
+	gain = gain + 0.0001f * (190.0f - mag);
+	return (0.0f > gain) ? 0.0f : gain;
 }
 
 /* dsp/agc.c:13-25 */
@@ -296,6 +325,19 @@ md_wrap_2pi(float xf)
 	}
 	return r;
 }
+
+/* The same in two pieces, for a caller that votes on `far` together with its other rare events (rotwin_body.h): the branch-free
+ * part, and what a lane with far set takes instead.  (Written out next to md_wrap_2pi, not under it: the latency kernel's
+ * compilation is sensitive to the order of md_wrap_2pi's comparisons.) */
+__device__ __forceinline__ float
+md_wrap_2pi_near(float xf, bool &far)
+{
+	const bool wraps = !(fabsf(xf) < MD_TWO_PI_F);
+	const float once = (xf < 0.0f) ? (xf + MD_TWO_PI_F) + MD_TWO_PI_LO : (xf - MD_TWO_PI_F) - MD_TWO_PI_LO;
+	far = !(fabsf(xf) < MD_FOUR_PI_F);
+	return wraps ? once : xf;
+}
+__device__ __forceinline__ float md_wrap_2pi_far(float xf) { return (float)fmod((double)xf, MD_TWO_PI_D); }
 
 /* pll.c:154-159 */
 /* Branch free: v > 15 reads lut[31] = (float)tanh(15) and v < -16 reads lut[0] = (float)tanh(-16), which ARE
@@ -436,6 +478,44 @@ md_pll_update_packed(PllWord &p, uint32_t &fl, const float *lut, float alpha, fl
 	fl = (p.freq >= fmax) ? (fl & ~4u) : ((p.freq <= -fmax) ? (fl | 4u) : fl);
 	p.freq = md_clamp_sym(p.freq, fmax);                                    /* MAX(-fmax, MIN(fmax, freq)) */
 	return lock_now | unlock_now;
+}
+
+/* md_pll_update_packed<false, true> in two pieces, for a caller that votes ONCE on all the rare events of a symbol and repairs them out
+ * of line (the rotating-window body's rare-path policy, rotwin_body.h).  md_pll_update_common is the straight line: no branch, no
+ * flag arithmetic, and no clamp of the frequency yet.  It returns the mask of the lanes with a lock event or at +-fmax; ph and far
+ * are md_wrap_2pi_near's (a lane with far set needs p.phase = md_wrap_2pi_far(ph)).  md_pll_update_rare is pll_flags_step on the
+ * lane's own conditions - the identity for a lane without an event, so the whole wave may run it - and returns `changed`.  The
+ * caller clamps the frequency behind both (md_clamp_sym(p.freq, fmax): the turn-round asks the frequency before the clamp).  The
+ * float and double operations and their order are md_pll_update_packed's. */
+__device__ __forceinline__ uint64_t
+md_pll_update_common(PllWord &p, uint32_t fl, const float *lut, float alpha, float beta, float fmax, float i, float q, float &ph, bool &far)
+{
+	const float ti = md_tanh_lut(lut, i), tq = md_tanh_lut(lut, q);
+	const float e = ti * q - tq * i;                                        /* pll.c:143-151 */
+
+	ph = p.phase + alpha * e;
+	p.phase = md_wrap_2pi_near(ph, far);                                    /* pll.c:113 */
+	p.freq = p.freq + beta * e;
+
+	const float decayed = p.err * (1.0f - 0.001f);
+	p.err = (float)((double)decayed + fabs((double)e) * (double)0.001f);    /* pll.c:117 */
+
+	const uint64_t m_below = __builtin_amdgcn_ballot_w64(p.err < 85.0f), m_above = __builtin_amdgcn_ballot_w64(p.err > 105.0f);
+	const uint64_t m_locked = __builtin_amdgcn_ballot_w64((fl & 1u) != 0);
+	const uint64_t m_lock_event = (m_below & ~m_locked) | (m_above & m_locked);
+	const float swept = (float)((double)p.freq + ((fl & 4u) ? 0.000001 : -0.000001));       /* pll.c:125 */
+	p.freq = md_lane_select(m_locked ^ m_lock_event, swept, p.freq);
+	const uint64_t m_turn = __builtin_amdgcn_ballot_w64(fabsf(p.freq) >= fmax);     /* pll.c:126-127 have something to do */
+	return m_lock_event | m_turn;
+}
+
+__device__ __forceinline__ uint32_t
+md_pll_update_rare(const PllWord &p, uint32_t &fl, float fmax, uint32_t &first)
+{
+	const PllFlagStep s = pll_flags_step(fl, p.err < 85.0f ? 1u : 0u, p.err > 105.0f ? 1u : 0u,
+	                                     p.freq >= fmax ? PLL_FREQ_HIGH : (p.freq <= -fmax ? PLL_FREQ_LOW : PLL_FREQ_INSIDE));
+	fl = s.fl; first = s.first;
+	return s.changed;
 }
 
 /* timing.c:60-87,90-95 */

@@ -46,6 +46,7 @@ struct WinG {
 	                     BLOCK = MDEMOD_RW_BLOCK, ROTN = 1, RING = 32, REGSLOTS = 0;
 	static constexpr bool GATHER = true, SCALAR_SLIDE = false, VCONST = false;
 	static constexpr bool LOCK_EARLY_OUT = true;        /* the lock detector's flag arithmetic behind one wave vote (demod_device.h: md_pll_update_packed) */
+	static constexpr bool RARE_ONE_BRANCH = false;       /* (rotwin_body.h: the std window's) */
 	static_assert(NS % G == 0 && NS / G <= 36, "whole 16-byte loads, and few enough of them to stay in registers");
 	typedef typename RFmt<FMT>::sample_t sample_t;
 	__device__ __forceinline__ void setup(uint32_t) {}

@@ -98,6 +98,7 @@ struct WinP {
 	                     MAXSL = GeoP<GEO>::MAXSL, DEPTH = GeoP<GEO>::DEPTH, BLOCK = GeoP<GEO>::BLOCK, NCH = NW / SLIDE, GD = FMT == 16 ? 16 : 8, REGSLOTS = 0, ROTN = NCH, RING = 32;
 	static constexpr bool GATHER = false, SCALAR_SLIDE = false, VCONST = false;      /* (rotwin_body.h: the std window's scalar slide and VGPR constants) */
 	static constexpr bool LOCK_EARLY_OUT = true;        /* the lock detector's flag arithmetic behind one wave vote (demod_device.h: md_pll_update_packed) */
+	static constexpr bool RARE_ONE_BRANCH = false;       /* (rotwin_body.h: the std window's) */
 	__device__ __forceinline__ void setup(uint32_t) {}
 	static_assert(kBack % SLIDE == 0 && NW % SLIDE == 0, "history and window are whole chunks");
 

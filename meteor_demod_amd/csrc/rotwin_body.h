@@ -13,8 +13,10 @@
  *     fir(ctab_addr, a, bank, C, rot, re, im)      filter.c:46-65 for a lane whose taps start `a` slots into the window
  * and the geometry (kTaps, kBack, NW, SLIDE, AMAX, MAXSL, BLOCK, ROTN: rotations before the window is where it started,
  * RING: symbols of the per-lane output ring; LOCK_EARLY_OUT: the lock detector's flag arithmetic behind one wave vote,
- * md_pll_update_packed in demod_device.h).  Everything else - symbol clock, AGC, NCO, loops, lock
- * detector, output ring, state and history hand-over - is here, compiled for the registers the policy leaves to hipcc.
+ * md_pll_update_packed in demod_device.h; RARE_ONE_BRANCH: the scalar stage of a firing computes the lane masks of its rare events
+ * - the short cabsf's fallback, two symbols in one input sample, the far phase wrap, a lock event or turn-round - without branching
+ * on any, ORs them on the scalar unit and repairs all of them in ONE block laid out of line, in front of the ring write).
+ * Everything else - symbol clock, AGC, NCO, loops, lock detector, output ring, state and history hand-over - is here, compiled for the registers the policy leaves to hipcc.
  */
 #ifndef MDEMOD_ROTWIN_BODY_H
 #define MDEMOD_ROTWIN_BODY_H
@@ -183,6 +185,7 @@ rotwin_demod(const DemodLaunch &L)
 #ifndef ROT_PRIO_LEVEL
 #define ROT_PRIO_LEVEL 2
 #endif
+	constexpr bool RARE = W::RARE_ONE_BRANCH;
 	constexpr int PRIO = ROT_PRIO;               /* the scalar stage of a firing (and the symbol clock inside it) at raised wave priority, the FIR and the slide at 0 (NOTEBOOK.md 5.0: +5 % on configs[1] when round 2 found it) */
 
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -413,7 +416,15 @@ rotwin_demod(const DemodLaunch &L)
 			n_fir++;
 #endif
 
-			y = md_agc<(KS == 14 && !OQPSK && LUT)>(y, r_gain, r_bias_re, r_bias_im);        /* (the configs[1] instance: the short cabsf, demod_device.h) */
+			/* (the configs[1] instance: the short cabsf, demod_device.h.  RARE: its fallback is one of the events of the rare block below,
+			 * which takes the magnitude again from the scaled sample; agc.c:22-24 follow behind that block) */
+			constexpr bool SHORT_ABS = KS == 14 && !OQPSK && LUT;      /* (never OQPSK: with RARE the gain follows in the symbol's half of a firing) */
+			float mag = 0.0f;
+			uint64_t m_abs = 0;                        /* lanes whose short root has to be redone exactly */
+			if constexpr (RARE && SHORT_ABS) {
+				y = md_agc_apply(y, r_gain, r_bias_re, r_bias_im);
+				mag = md_cabsf_short_try(y.re, y.im, m_abs);
+			} else y = md_agc<SHORT_ABS>(y, r_gain, r_bias_re, r_bias_im);
 			uint32_t fl = (uint32_t)ld_flags();          /* bit 0 locked, 1 locked_once, 2 updown > 0, 3 overflow */
 			PllWord pll;
 			pll.phase = r_phase; pll.freq = r_freq;
@@ -442,21 +453,28 @@ rotwin_demod(const DemodLaunch &L)
 			}
 			md_nco_advance<true>(pll.phase, pll.freq);
 
+			/* demod.c:33-47: only the LAST symbol fired inside one input sample survives (found by fuzzing in round 2: NOTEBOOK.md 5.0);
+			 * the ring goes back by one symbol */
+			uint64_t m_again = 0;
+			auto ring_back = [&]() {                   /* (never the first symbol of a call: lastv starts at -1) */
+				const uint32_t prev = sym_count() - 1u;
+				st_symbase(prev & ~(uint32_t)(RING - 1));
+				ring_off = rot_ring_off(prev, RING, BLOCK);
+			};
 			if (emit) {
-				/* demod.c:33-47: only the LAST symbol fired inside one input sample survives (found by fuzzing in round 2: NOTEBOOK.md 5.0) */
 				const bool again = (v_cur == ld_lastv());
+				/* (RARE: the mask is taken HERE, where the old lastv and v_cur still are what the loop carries - left to the rare
+				 * block's vote the comparison sinks behind the clock, and both words get a second register and a copy) */
+				if constexpr (RARE) { m_again = __builtin_amdgcn_ballot_w64(again); asm volatile("" : "+s"(m_again)); }
 				/* (in a register the word is copied HERE, behind the compiler's back: left to the loop's phi the copy comes after the
 				 * clock, which then has to advance a second version of v_cur - two more copies round the loop) */
 				int lastv = v_cur;
 				if constexpr ((RS & 8) != 0) asm("" : "+v"(lastv));
 				st_lastv(lastv);
-				if (__builtin_expect(md_any(again), 0)) {
-					if (again) {                       /* (never the first symbol of a call: lastv starts at -1) */
-						const uint32_t prev = sym_count() - 1u;
-						st_symbase(prev & ~(uint32_t)(RING - 1));
-						ring_off = rot_ring_off(prev, RING, BLOCK);
+				if constexpr (!RARE)
+					if (__builtin_expect(md_any(again), 0)) {
+						if (again) ring_back();
 					}
-				}
 				float t_prev = ld_tprev();
 				md_timing_update(t_phase, t_freq, t_prev, k_t_alpha, k_t_beta, k_t_center, C.t_maxdev, out_im);
 				st_tprev(t_prev);
@@ -471,17 +489,40 @@ rotwin_demod(const DemodLaunch &L)
 #endif
 			if (emit) {
 				uint32_t first = 0;
-				const uint32_t changed = md_pll_update_packed<false, W::LOCK_EARLY_OUT>(pll,fl, lut, k_pll_alpha, k_pll_beta, C.pll_fmax, out_re, out_im, first);
-				if (__builtin_expect(changed != 0, 0)) {          /* a plain divergent branch: skipped when no lane of the wave takes it */
+				auto lock_event = [&](uint32_t fl_now) {
 					const uint32_t sym_now = sym_count();
 					if (first) sli[S_FIRSTLOCK * 64] = (int)sym_now;
 					const int ev_call = sli[S_EVCALL * 64];
 					if (ev_call < MDEMOD_MAX_LOCK_EVENTS) {
 						mdemod_lock_event ev;
-						ev.symbol = L.st.n_symbols[stream] + sym_now; ev.locked = (int)(fl & 1u); ev.pad = 0;
+						ev.symbol = L.st.n_symbols[stream] + sym_now; ev.locked = (int)(fl_now & 1u); ev.pad = 0;
 						L.st.events[(size_t)stream * MDEMOD_MAX_LOCK_EVENTS + ev_call] = ev;
 					}
 					sli[S_EVCALL * 64] = ev_call + 1;
+				};
+				if constexpr (RARE) {
+					float ph;
+					bool far;
+					const uint64_t m_pll = md_pll_update_common(pll, fl, lut, k_pll_alpha, k_pll_beta, C.pll_fmax, out_re, out_im, ph, far);
+					/* every rare event of this symbol as a lane mask, OR-ed on the scalar unit: one scalar branch, not taken */
+					const uint64_t rare = m_pll | __builtin_amdgcn_ballot_w64(far) | m_again | m_abs;
+					if (__builtin_expect(rare != 0ull, 0)) {
+						/* each repair for the lanes it concerns; none reads what another writes, but the ring goes back before the lock
+						 * event asks it for the symbol's number */
+						if (md_lane_bit(m_abs)) mag = md_cabsf_exact(y.re, y.im);          /* agc.c:21 */
+						if (md_lane_bit(m_again)) ring_back();
+						if (far) pll.phase = md_wrap_2pi_far(ph);
+						/* (the new flag word is made beside the old one and moved over it by hand: a word the block redefines while
+						 * the old one is still read is two registers to the compiler, which then copies it on the common way too) */
+						uint32_t fl_new = fl;
+						if (md_pll_update_rare(pll, fl_new, C.pll_fmax, first)) lock_event(fl_new);
+						asm volatile("v_mov_b32 %0, %1" : "+v"(fl) : "v"(fl_new));
+					}
+					pll.freq = md_clamp_sym(pll.freq, C.pll_fmax);         /* MAX(-fmax, MIN(fmax, freq)), behind the turn-round's question */
+					if constexpr (SHORT_ABS) r_gain = md_agc_gain_step(r_gain, mag);      /* agc.c:22-24 */
+				} else {
+					const uint32_t changed = md_pll_update_packed<false, W::LOCK_EARLY_OUT>(pll,fl, lut, k_pll_alpha, k_pll_beta, C.pll_fmax, out_re, out_im, first);
+					if (__builtin_expect(changed != 0, 0)) lock_event(fl);   /* a plain divergent branch: skipped when no lane of the wave takes it */
 				}
 				const uint32_t sym = (uint32_t)(md_quantise(out_re) & 0xFF) | ((uint32_t)(md_quantise(out_im) & 0xFF) << 8);
 				/* RING-symbol ring per lane in LDS, [16-byte group][thread]; every RING symbols one full run (64 bytes for 32) goes out */
