@@ -177,7 +177,7 @@ int  mdemod_device_count(void);
 int  mdemod_create(const mdemod_params *params, mdemod_ctx **out);
 /* Replaces demod_deinit (demod.c:18-21). */
 void mdemod_destroy(mdemod_ctx *ctx);
-/* Put every stream back into the reference's power-on state. */
+/* Put every stream back into the reference's power-on state.  Asynchronous on hip_stream. */
 int  mdemod_reset(mdemod_ctx *ctx, void *hip_stream);
 
 /* Soft-symbol capacity (in SYMBOLS) that is always enough for n input samples: one symbol per
@@ -192,7 +192,8 @@ uint64_t mdemod_max_symbols(const mdemod_ctx *ctx, uint64_t n_samples);
 uint64_t mdemod_nominal_pitch(const mdemod_ctx *ctx, uint64_t n_samples);
 /* Copy the symbols the LAST process call wrote (per-stream counts kept by the context) from rows of soft_stride_symbols
  * to rows of out_pitch_symbols (both multiples of 8; 16-byte moves): the compaction in front of a PCIe copy or of the
- * RCCL fan-in of soft-symbol buffers (main.c:305-315 writes symbols back to back; the hard-bound pitch is a GPU artefact). */
+ * RCCL fan-in of soft-symbol buffers (main.c:305-315 writes symbols back to back; the hard-bound pitch is a GPU artefact).
+ * Asynchronous on hip_stream, behind the process call whose counts it reads. */
 int  mdemod_compact_soft(mdemod_ctx *ctx, const int8_t *soft_dev, uint64_t soft_stride_symbols,
                          int8_t *out_dev, uint64_t out_pitch_symbols, void *hip_stream);
 /* The fan-in of soft-symbol buffers for a host that drives several GPUs from ONE process (host/meteor_demod_amd.c --devices: one worker
@@ -223,6 +224,7 @@ int  mdemod_process_device_uniform(mdemod_ctx *ctx,
 /*
  * Ragged batch: per-stream sample offsets (from iq_dev, in IQ samples) and
  * counts, both arrays of n_streams entries in DEVICE memory.  count 0 is legal.
+ * Asynchronous on hip_stream.
  */
 int  mdemod_process_device(mdemod_ctx *ctx,
                            const void *iq_dev,
@@ -256,25 +258,32 @@ int  mdemod_process_host(mdemod_ctx *ctx,
 int  mdemod_pin_host_buffer(mdemod_ctx *ctx, const void *base, size_t bytes);
 int  mdemod_unpin_host_buffer(mdemod_ctx *ctx, const void *base);
 
-/* ---- status / state (synchronise with the last call on hip_stream first) -- */
+/* ---- status / state --------------------------------------------------------
+ * Every call of this block is synchronous: its copies are queued on hip_stream, behind the last call queued there, and it waits for
+ * hip_stream before it returns (the host memory is read or written when it does). */
 
+/* Synchronous (waits for hip_stream). */
 int  mdemod_get_status(mdemod_ctx *ctx, uint32_t first, uint32_t count,
                        mdemod_status *out, void *hip_stream);
+/* Synchronous (waits for hip_stream). */
 int  mdemod_get_lock_events(mdemod_ctx *ctx, uint32_t stream,
                             mdemod_lock_event *out, uint32_t cap, uint32_t *n,
                             void *hip_stream);
+/* Synchronous (waits for hip_stream). */
 int  mdemod_get_state(mdemod_ctx *ctx, uint32_t stream, mdemod_stream_state *out,
                       void *hip_stream);
 /* MDEMOD_ERR_PARAM for a carrier state the reference's loop cannot hold: |pll_phase| + |pll_freq| >= 12.5 (pll.c:113
  * keeps the phase inside (-2pi, 2pi), pll.c:126-128 the frequency word inside +-fmax), or a clock word t_freq further than
  * centre / 4096 from the centre 2 pi symrate / (samplerate * interp_factor) (timing.c:80-86 keeps it there; a state exported
- * by mdemod_get_state always passes). */
+ * by mdemod_get_state always passes).  Synchronous (waits for hip_stream). */
 int  mdemod_set_state(mdemod_ctx *ctx, uint32_t stream, const mdemod_stream_state *in,
                       void *hip_stream);
 /* Filter history: the last mdemod_history_len() input samples, oldest first,
  * as float I,Q pairs (filter.h:6). */
 uint32_t mdemod_history_len(const mdemod_ctx *ctx);
+/* Synchronous (waits for hip_stream). */
 int  mdemod_get_history(mdemod_ctx *ctx, uint32_t stream, float *iq_pairs, void *hip_stream);
+/* Synchronous (waits for hip_stream). */
 int  mdemod_set_history(mdemod_ctx *ctx, uint32_t stream, const float *iq_pairs, void *hip_stream);
 
 /* ---- overlapped tiles of ONE recording ------------------------------------ */

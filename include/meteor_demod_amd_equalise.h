@@ -89,7 +89,7 @@ int  mdemod_equalise_tables_device(const uint8_t *picture_dev, const uint8_t *va
 int  mdemod_equalise_apply_device(const uint8_t *picture_dev, const uint8_t *valid_dev, uint32_t width, uint32_t height, uint32_t planes,
                                   const mdemod_equalise_opts *opts, const void *work_dev, uint8_t *out_dev, int device, void *hip_stream);
 
-/* Both, one after the other on hip_stream. */
+/* Both, one after the other on hip_stream; asynchronous. */
 int  mdemod_equalise_device(const uint8_t *picture_dev, const uint8_t *valid_dev, uint32_t width, uint32_t height, uint32_t planes,
                             const mdemod_equalise_opts *opts, void *work_dev, uint64_t work_bytes, uint8_t *out_dev, int device, void *hip_stream);
 

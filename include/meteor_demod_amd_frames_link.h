@@ -20,7 +20,8 @@ extern "C" {
 uint64_t mdemod_frames_link_windows(const mdemod_frames_link *link, uint64_t m);
 
 /* mdemod_frames_candidates_device under `link`: cand_dev[mdemod_frames_link_windows(link, m)]; candidate.hypothesis carries H (with
- * `differential` only h in {0, 1, 4, 5}, and the score is the absolute value).  Nothing outside soft_dev[0 .. m) is read. */
+ * `differential` only h in {0, 1, 4, 5}, and the score is the absolute value).  Nothing outside soft_dev[0 .. m) is read.  Queued on
+ * hip_stream of `device`; asynchronous. */
 int  mdemod_frames_link_candidates_device(const mdemod_frames_link *link, const int8_t *soft_dev, uint64_t m, mdemod_frames_candidate *cand_dev,
                                           int device, void *hip_stream);
 
@@ -30,12 +31,13 @@ int  mdemod_frames_link_track(const mdemod_frames_link *link, const mdemod_frame
                               uint64_t n_windows, uint64_t m, mdemod_frame_info *frames, uint64_t cap, uint64_t *n_frames);
 
 /* mdemod_frames_viterbi_device with the symbols taken through frames[].hypothesis = H and, with `differential`, the NRZ-M undone
- * at traceback; channel_errors is counted on the decoder's own bits.  The same refusals for H as mdemod_frames_link_track. */
+ * at traceback; channel_errors is counted on the decoder's own bits.  The same refusals for H as mdemod_frames_link_track.
+ * Synchronous. */
 int  mdemod_frames_link_viterbi_device(const mdemod_frames_link *link, const int8_t *soft_dev, uint64_t m, mdemod_frame_info *frames,
                                        uint64_t n_frames, uint8_t *cadu_dev, int device, void *hip_stream);
 
 /* All three steps, as mdemod_frames_decode_device / mdemod_frames_decode_host.  The host entry's pieces are one symbol longer with
- * `skew` (the correlator's 33; the sub-blocks' 128 + 1 on the right); its result is byte for byte the device entry's. */
+ * `skew` (the correlator's 33; the sub-blocks' 128 + 1 on the right); its result is byte for byte the device entry's.  Synchronous. */
 int  mdemod_frames_link_decode_device(const mdemod_frames_link *link, const mdemod_frames_opts *opts, const int8_t *soft_dev, uint64_t m,
                                       uint8_t *cadu, mdemod_frame_info *frames, uint64_t cap, uint64_t *n_frames, int device, void *hip_stream);
 int  mdemod_frames_link_decode_host(const mdemod_frames_link *link, const mdemod_frames_opts *opts, const int8_t *soft, uint64_t m,

@@ -56,7 +56,8 @@ int  mdemod_fe_design(const mdemod_params *input, const mdemod_fe_params *fe, fl
  * bps = 32 (everything else, reserved flags included, is input's).  Refusals of that context's mdemod_create pass through. */
 int  mdemod_fe_create(const mdemod_params *input, const mdemod_fe_params *fe, mdemod_fe **out);
 void mdemod_fe_destroy(mdemod_fe *fe);
-/* Every stream back to its power-on state: NCO index, filter history AND the inner demodulator (mdemod_reset). */
+/* Every stream back to its power-on state: NCO index, filter history AND the inner demodulator (mdemod_reset).  Asynchronous
+ * on hip_stream. */
 int  mdemod_fe_reset(mdemod_fe *fe, void *hip_stream);
 /* The inner demodulator (status, lock events, state, kernel name: include/meteor_demod_amd.h); owned by fe. */
 mdemod_ctx *mdemod_fe_demodulator(mdemod_fe *fe);

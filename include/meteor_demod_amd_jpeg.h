@@ -78,7 +78,7 @@ int  mdemod_jpeg_encode_device(const uint8_t *picture_dev, uint32_t width, uint3
 
 /* The second stage alone: coef_dev[n_mcus planes][64] (any int16; clamped as the header says) into the segments and the RSTm
  * between them at out_dev[0 .. out_room): no head, no EOI.  result_dev as above.  coef_dev and work_dev at multiples of 16 bytes,
- * n_mcus 1 .. 2^21. */
+ * n_mcus 1 .. 2^21.  Queued on hip_stream of `device`; asynchronous. */
 int  mdemod_jpeg_entropy_device(const int16_t *coef_dev, uint64_t n_mcus, uint32_t planes, uint32_t restart_interval, uint8_t *out_dev, uint64_t out_room,
                                 uint64_t *result_dev, void *work_dev, uint64_t work_bytes, int device, void *hip_stream);
 

@@ -80,7 +80,8 @@ int  mdemod_png_encode_device(const uint8_t *picture_dev, const uint8_t *valid_d
                               uint8_t *out_dev, uint64_t out_room, uint64_t *result_dev, void *work_dev, uint64_t work_bytes, int device, void *hip_stream);
 
 /* The second stage alone: bytes_dev[n_bytes] (any bytes; 1 .. 2^30 of them, at a multiple of 16 bytes) into the segments' IDAT chunks
- * at out_dev[0 .. out_room): no head, no Adler chunk, no IEND; the last segment carries BFINAL.  result_dev as above. */
+ * at out_dev[0 .. out_room): no head, no Adler chunk, no IEND; the last segment carries BFINAL.  result_dev as above.  Queued on
+ * hip_stream of `device`; asynchronous. */
 int  mdemod_png_deflate_device(const uint8_t *bytes_dev, uint64_t n_bytes, uint32_t segment, uint8_t *out_dev, uint64_t out_room, uint64_t *result_dev, void *work_dev,
                                uint64_t work_bytes, int device, void *hip_stream);
 

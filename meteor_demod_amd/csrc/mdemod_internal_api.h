@@ -39,20 +39,22 @@ int  mdemod_set_state_all(mdemod_ctx *ctx, const mdemod_stream_state *seed, void
  * from its predecessor onto the predecessor's constellation rotation.  In OQPSK
  * mode an odd number of quarter turns also moves the symbol clock by half a symbol
  * (t_phase +- pi, dual state toggled: the rails swap and their firings are half a
- * symbol apart). */
+ * symbol apart).  Asynchronous on hip_stream. */
 int  mdemod_rotate_carrier(mdemod_ctx *ctx, const int32_t *quarter_turns_dev, void *hip_stream);
 
 /* Per-stream carrier seeds (device arrays of n_streams entries): pll frequency in rad/symbol and sweep direction
  * (+1 / -1, pll.c:112) of stream s := freq_dev[s], updown_dev[s]; everything else is left as it is.  Used with
- * mdemod_set_state_all when the carrier moves along the recording (Doppler) and every tile needs its local estimate. */
+ * mdemod_set_state_all when the carrier moves along the recording (Doppler) and every tile needs its local estimate.  Asynchronous
+ * on hip_stream. */
 int  mdemod_set_carrier_seeds(mdemod_ctx *ctx, const float *freq_dev, const int32_t *updown_dev, void *hip_stream);
 /* Per-stream AGC gain seeds (agc.c:9, device array of n_streams entries, negative values become 0 like agc.c:23):
- * for tiles of a recording whose amplitude changes faster than the reference's AGC follows at that gain. */
+ * for tiles of a recording whose amplitude changes faster than the reference's AGC follows at that gain.  Asynchronous on hip_stream. */
 int  mdemod_set_gain_seeds(mdemod_ctx *ctx, const float *gain_dev, void *hip_stream);
 
 /* Per-stream symbol-clock frequency seeds (timing.c:14 `freq`, rad per interpolated sample; device array of n_streams entries).
  * Words outside centre +- centre / 4096 - what timing.c:80-86 can hold, and what the kernels' symbol clock counts on - are clamped to
- * that range on the device as they are copied in (mdemod_set_state refuses such a word; a device array cannot be refused). */
+ * that range on the device as they are copied in (mdemod_set_state refuses such a word; a device array cannot be refused).
+ * Asynchronous on hip_stream. */
 int  mdemod_set_clock_seeds(mdemod_ctx *ctx, const float *t_freq_dev, void *hip_stream);
 /* mdemod_get_state for `count` streams from `first` in one round trip (tiles of a recording: thousands of streams). */
 int  mdemod_get_states(mdemod_ctx *ctx, uint32_t first, uint32_t count, mdemod_stream_state *out, void *hip_stream);
